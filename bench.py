@@ -13,10 +13,16 @@ Extra objects on the JSON line:
   roofline      dominant kernel's algorithmic FLOP per launch / its average launch
                 duration (hipEvents recorded by the library on the launch stream
                 during the timed region), against the bf16x3 effective peak.
-  cpu_baseline  the torch-CPU restatement of the same forward (oracle/), rank 0 at
-                N = 1 only, on a bounded sample.
+  cpu_baseline  with --full: the torch-CPU restatement of the same forward (oracle/), rank 0
+                at N = 1 only, on a bounded sample ('check' = the timed batch against it).
+  extra_configs with --full, default 1-GPU run: the other BASELINE configurations, the train
+                steps and the eval-loop batch, each a run of its own after the headline.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--model hardnet|wang2|...|fdl_NASNet|fdl_NASNet_01]
+A plain run sets up, warms up, times the K steps and prints the line; --dump-outputs DIR also
+writes the last timed step's outputs as DIR/<name>.npy.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+                       [--model hardnet|wang2|...|fdl_NASNet|fdl_NASNet_01]
 For N > 1 launch with torch.distributed.run (one process per GPU).
 """
 from __future__ import annotations
@@ -483,6 +489,24 @@ SIMDS = 256 * 4
 VALU_ISSUE_CYC = 2        # cycles per wave64 VALU instruction on a SIMD-32 (MI355X_MICROARCH.md)
 
 
+DUMP_ARRAY_BYTES = 16 << 20  # per dumped array; a run dumps at most four (64 MB in all)
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """--dump-outputs: each array as <path>/<name>.npy in float32.  An array above DUMP_ARRAY_BYTES is cut to
+    a fixed sample of its rows (numpy default_rng(0), sorted, the same rows every run); the chosen rows go
+    beside it as <name>_rows.npy (float64, exact for any row index)."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.dim() > 0 and t.numel() * 4 > DUMP_ARRAY_BYTES:
+            keep = max(1, DUMP_ARRAY_BYTES // (4 * (t.numel() // t.shape[0])))
+            rows = np.sort(np.random.default_rng(0).choice(t.shape[0], size=keep, replace=False))
+            t = t[torch.from_numpy(rows).to(t.device)]
+            np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
+
+
 def run(opts, world, rank, local, dev, on_gpu, backend):
     """One measured configuration: W warmup steps, then K timed steps bracketed by a barrier and a
     device synchronisation on both sides; max over ranks.  Returns rank 0's result dict."""
@@ -598,6 +622,13 @@ def run(opts, world, rank, local, dev, on_gpu, backend):
     value = total / elapsed / 1e6
     if rank != 0:
         return None
+    if getattr(opts, "dump_outputs", None):
+        # what a caller of the timed step holds after its last step (the inputs are seeded: the same
+        # arguments give the same arrays from run to run)
+        arrays = {"descriptors": gathered if (gathered is not None and not opts.no_allgather) else out}
+        if cfg5:
+            arrays.update({k: last[k] for k in ("loss", "pos", "min_neg") if k in last})
+        dump_outputs(opts.dump_outputs, arrays)
     roof = None
     if on_gpu:
         stages_ms = {k: round(v[0] / opts.steps, 3) for k, v in stages.items()}
@@ -726,7 +757,7 @@ def run(opts, world, rank, local, dev, on_gpu, backend):
     if cfg5:
         result["pairs_per_s"] = round(pairs * opts.steps / elapsed, 1)
         result["loss"] = float(last["loss"].item()) if "loss" in last else None
-    if world == 1 and on_gpu and not opts.no_cpu_baseline:
+    if world == 1 and on_gpu and opts.full and not opts.no_cpu_baseline:
         if cfg5:
             cb, check = cpu_baseline_pairs(model, opts.cpu_seconds), check_pairs(out, pairs, last["pos"],
                                                                                    last["min_neg"])
@@ -1102,12 +1133,21 @@ def main():
                          "raw uint8 patches (64x64, or 32x32 for u8-none) with the loader's resize / "
                          "ToTensor / Normalize fused into the forward (hn_forward_u8, SURVEY 8(f) row 3)")
     ap.add_argument("--no-allgather", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps also run the CPU baseline with the oracle check of "
+                         "the timed batch ('cpu_baseline', 'gpu_vs_cpu', 'check') and, on a default 1-GPU run of "
+                         "config 2, the other configurations ('extra_configs'); a plain run does neither")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-extra-configs", action="store_true",
-                    help="default 1-GPU runs of config 2 also measure configs 3 (wang2/3/4) and 5 after the "
-                         "headline line and attach them under 'extra_configs'; this skips them")
+                    help="with --full, default 1-GPU runs of config 2 also measure configs 3 (wang2/3/4) and 5 "
+                         "after the headline line and attach them under 'extra_configs'; this skips them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last of them computed (the descriptors; config 5: "
+                         "also loss, pos, min_neg) as DIR/<name>.npy, float32, large arrays as a fixed row sample")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.config == 5 and args.model != "hardnet":
         ap.error("config 5 is the stock HardNet pair step")
     if args.input.startswith("u8-") and (args.device != "cuda" or args.config == 5):
@@ -1133,13 +1173,13 @@ def main():
             dist.init_process_group("gloo")
 
     result = run(args, world, rank, local, dev, on_gpu, backend)
-    extras = (world == 1 and on_gpu and not args.no_extra_configs and args.model == "hardnet"
+    extras = (world == 1 and on_gpu and args.full and not args.no_extra_configs and args.model == "hardnet"
               and args.config in (None, 2) and args.batch is None and args.input == "f32")
     if extras:
         result["extra_configs"] = {}
         for key, model, cfg in EXTRA_CONFIGS:
             o = argparse.Namespace(**vars(args))
-            o.model, o.config, o.batch = model, cfg, None
+            o.model, o.config, o.batch, o.dump_outputs = model, cfg, None, None
             o.steps, o.warmup = max(3, args.steps // 2), max(1, args.warmup)
             o.cpu_seconds = min(args.cpu_seconds, 5.0 if cfg is None else 8.0)
             torch.cuda.empty_cache()

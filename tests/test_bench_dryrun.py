@@ -30,6 +30,27 @@ def _run(extra):
     return json.loads(lines[0])
 
 
+def test_dump_outputs_and_steps_single_process(tmp_path):
+    """--dump-outputs writes the last timed step's descriptors (float32, unit norm), identical from run to run
+    with the same arguments; --steps sets the timed steps; --full is accepted (on CPU nothing lies behind it)."""
+    import numpy as np
+    procs = []
+    for tag, extra in (("a", []), ("b", ["--full"])):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--device", "cpu", "--steps", "3",
+               "--warmup", "1", "--batch", "24", "--dump-outputs", str(tmp_path / tag)] + extra
+        procs.append(subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=ROOT,
+                                      env=dict(os.environ, OMP_NUM_THREADS="2")))
+    for p in procs:
+        out, err = p.communicate(timeout=600)
+        assert p.returncode == 0, err[-3000:]
+        d = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["cpu_baseline"] is None and "extra_configs" not in d
+    a, b = np.load(tmp_path / "a" / "descriptors.npy"), np.load(tmp_path / "b" / "descriptors.npy")
+    assert a.dtype == np.float32 and a.shape == (24, 128)
+    assert np.array_equal(a, b)
+    assert np.abs(np.linalg.norm(a, axis=1) - 1).max() < 1e-5
+
+
 def test_allgather_branch_world2():
     d = _run(["--batch", "48"])
     assert d["n_gpus"] == 2 and d["ranks_seen"] == 2 and d["scaling"] == "weak"

@@ -12,5 +12,5 @@ run() {  # name, seconds, args...
   if [ $rc -ne 0 ]; then exit $rc; fi
 }
 for m in ${MODELS:-hardnet c5 wang2 wang3 wang4 fdl_NASNet fdl_NASNet_01}; do
-  if [ "$m" = c5 ]; then run c5 300 --config 5 ${ARGS:-}; else run $m 300 --model $m ${ARGS:-}; fi
+  if [ "$m" = c5 ]; then run c5 300 --full --config 5 ${ARGS:-}; else run $m 300 --full --model $m ${ARGS:-}; fi
 done

@@ -16,6 +16,8 @@ run() {  # name, seconds, command...
   return 0
 }
 STEPS=${STEPS:-pytest,smoke,bench,prof}
+# the bench and prof steps cover the whole bench (CPU baselines / checks, extra configurations) unless told otherwise
+BENCH_ARGS=${BENCH_ARGS:---full --steps 20 --warmup 5}
 [[ $STEPS == *pytest* ]] && run pytest_gpu 500 python -u -m pytest ${PYTEST_FILES:-tests} -m gpu -q -rf --timeout 120 --timeout-method thread ${PYTEST_ARGS:-}
 [[ $STEPS == *smoke* ]] && run smoke 200 python -c "import __graft_entry__ as g; g.smoke()"
 [[ $STEPS == *bench* ]] && run bench 300 python bench.py ${BENCH_ARGS:---steps 20 --warmup 5}
