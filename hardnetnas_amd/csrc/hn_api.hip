@@ -969,6 +969,13 @@ static int64_t hardnet_sub(const hn_model* m, int64_t p) { return std::max<int64
 static int64_t hardnet_group(const hn_model* m, int64_t p) {
   return std::max(hardnet_sub(m, p), std::min<int64_t>(p, m->c12group));
 }
+// floats of the workspace's first region for chunks of up to p patches: conv3's output a3 (one sub-chunk, 16,384
+// floats per patch) and, once the chunk's conv5 launches have consumed it, the small-batch head's split-K
+// partials (8,192 floats per patch of a chunk of up to kHeadSplitMaxP) -- sized for both, so which head runs does
+// not depend on HN_SUBCHUNK (the unsplit head sums K in another order).  At the default knobs a3 is the larger.
+static size_t hardnet_a3_floats(const hn_model* m, int64_t p) {
+  return std::max((size_t)16384 * hardnet_sub(m, p), (size_t)8192 * std::min<int64_t>(p, kHeadSplitMaxP));
+}
 
 // the chunk pipeline (forward_hardnet_pipe): a HardNet batch of more than one chunk, one k_c12 group per chunk
 static bool hardnet_pipelined(const hn_model* m, int64_t batch) {
@@ -979,7 +986,7 @@ extern "C" int hn_workspace_bytes(const hn_model* m, int64_t batch, size_t* byte
   if (!m || !bytes_out || batch < 0) return fail(HN_ERR_ARG, "bad argument");
   const int64_t p = batch < m->chunk ? batch : m->chunk;
   if (hardnet_subchunked(m)) {
-    *bytes_out = ((size_t)(hardnet_sub(m, p) + hardnet_group(m, p)) * 16384 + (size_t)p * 8192) * sizeof(float);
+    *bytes_out = (hardnet_a3_floats(m, p) + (size_t)hardnet_group(m, p) * 16384 + (size_t)p * 8192) * sizeof(float);
     // the pipeline's second k_c12 output buffer (64 KiB per patch of a chunk)
     if (hardnet_pipelined(m, batch)) *bytes_out += (size_t)p * 16384 * sizeof(float);
   } else {
@@ -1036,11 +1043,11 @@ static int forward_hardnet(hn_model* m, const float* in, int P, int pmax, float*
     // Mpatches/s for 16,384-patch launches; k_c12s 20.9 -> 18.5 ms per 262,144-patch step, conv4 7.3 ->
     // 8.2; a 65,536 group over 16,384 sub-chunks measured 5.26-5.29).  The head GEMM runs
     // once per chunk over the a5 of all sub-chunks.  conv4 writes its output over the sub-chunk's a2 slots,
-    // which conv3 has consumed.  Workspace (hn_workspace_bytes): [a3: sub x 64 KiB] [a2 / a4: group x 64 KiB]
-    // [a5: pmax x 32 KiB]
+    // which conv3 has consumed.  Workspace (hn_workspace_bytes): [a3 / head partials: hardnet_a3_floats]
+    // [a2 / a4: group x 64 KiB] [a5: pmax x 32 KiB]
     const int sub = (int)hardnet_sub(m, P), grp = (int)hardnet_group(m, P);
     a0 = ws;
-    a2 = ws + (size_t)16384 * hardnet_sub(m, pmax);
+    a2 = ws + hardnet_a3_floats(m, pmax);
     a1 = a2 + (size_t)16384 * hardnet_group(m, pmax);
     for (int g0 = 0; g0 < P; g0 += grp) {
       const int ng = std::min(grp, P - g0);
@@ -1053,10 +1060,9 @@ static int forward_hardnet(hn_model* m, const float* in, int P, int pmax, float*
       }
       if (int rc = hardnet_convs(m, a2, ng, sub, a0, a1 + (size_t)g0 * 8192, st)) return rc;
     }
-    // a0 -- conv3's output, consumed -- holds the small-batch head's split-K partials (8,192 floats per patch
-    // against its 16,384 per sub-chunk patch)
-    float* const hs = (size_t)16384 * hardnet_sub(m, pmax) >= (size_t)8192 * P ? a0 : nullptr;
-    STAGE("head", hn_launch_head(a1, out, m->hd.wpack[6], m->hd.bias[6], P, 8192, m->desc.l2_eps, st, false, hs));
+    // a0 -- conv3's output, consumed -- holds the small-batch head's split-K partials (8,192 floats per patch of a
+    // chunk of up to kHeadSplitMaxP: hardnet_a3_floats(pmax) covers them whatever the sub-chunk size)
+    STAGE("head", hn_launch_head(a1, out, m->hd.wpack[6], m->hd.bias[6], P, 8192, m->desc.l2_eps, st, false, a0));
     return HN_OK;
   } else {
     if (m->unfused_stem) {
@@ -1081,7 +1087,7 @@ static int forward_hardnet(hn_model* m, const float* in, int P, int pmax, float*
 // Order: c12(k + 1) waits until conv5(k - 1) has finished with its buffer (ev_free), conv3(k) waits for c12(k)
 // (ev_ready); conv3 .. head of consecutive chunks stay in order on the caller's stream, which waits for every
 // chunk's k_c12s -- the second stream is forked from and joined back into it (graph capture included).
-// Workspace: [a3: sub x 64 KiB] [a2 x 2: chunk x 64 KiB each] [a5: chunk x 32 KiB].
+// Workspace: [a3 / head partials: hardnet_a3_floats] [a2 x 2: chunk x 64 KiB each] [a5: chunk x 32 KiB].
 static int forward_hardnet_pipe(hn_model* m, const float* in, int64_t batch, float* out, float* ws, hipStream_t st) {
   std::lock_guard<std::mutex> lock(m->pipe_mu);
   if (!m->st2) {
@@ -1093,7 +1099,7 @@ static int forward_hardnet_pipe(hn_model* m, const float* in, int64_t batch, flo
   const int n = (int)((batch + C - 1) / C);
   const float ineps = m->desc.input_norm_eps;
   float* const a0 = ws;
-  float* const a2b[2] = {ws + (size_t)16384 * sub, ws + (size_t)16384 * sub + (size_t)16384 * C};
+  float* const a2b[2] = {ws + hardnet_a3_floats(m, C), ws + hardnet_a3_floats(m, C) + (size_t)16384 * C};
   float* const a1 = a2b[1] + (size_t)16384 * C;
   auto rows = [&](int k) { return (int)std::min<int64_t>(C, batch - (int64_t)k * C); };
   auto c12 = [&](int k, hipStream_t s) -> int {
@@ -1114,9 +1120,9 @@ static int forward_hardnet_pipe(hn_model* m, const float* in, int64_t batch, flo
     float* const a2 = a2b[k & 1];
     if (int rc = hardnet_convs(m, a2, P, sub, a0, a1, st)) return rc;
     if (k + 2 < n) HIPCHK(hipEventRecord(m->ev_free[k & 1], st));  // a2b[k & 1] free for c12(k + 2)
-    float* const hs = (size_t)16384 * sub >= (size_t)8192 * P ? a0 : nullptr;
+    // (the split-K partials in a0, as forward_hardnet: the k_c12 buffers are the second stream's by now)
     STAGE("head", hn_launch_head(a1, out + (size_t)k * C * 128, m->hd.wpack[6], m->hd.bias[6], P, 8192,
-                                 m->desc.l2_eps, st, false, hs));
+                                 m->desc.l2_eps, st, false, a0));
   }
   return HN_OK;
 }

@@ -93,8 +93,11 @@ int hn_create(const hn_arch_desc* desc, const float* host_params, size_t n_param
  * defaults that is 160 KiB per patch: 10 GiB from 65,536 patches up, 80 MiB at the reference eval loop's
  * 512.  Two environment knobs, read by hn_create, bound it for the stock HardNet (both default 65,536; any
  * values give bit-identical descriptors): HN_C12_GROUP (patches per fused stem+conv1+conv2 launch) and
- * HN_SUBCHUNK (patches per conv3..conv5 launch); the footprint is (HN_SUBCHUNK + HN_C12_GROUP) x 64 KiB +
- * chunk x 32 KiB, e.g. 4 GiB per 65,536-patch chunk at 16,384 / 16,384 (about 4 % slower end to end).
+ * HN_SUBCHUNK (patches per conv3..conv5 launch); the footprint is max(HN_SUBCHUNK x 64 KiB, min(chunk,
+ * 16,384) x 32 KiB) + HN_C12_GROUP x 64 KiB + chunk x 32 KiB, e.g. 4 GiB per 65,536-patch chunk at 16,384 /
+ * 16,384 (about 4 % slower end to end).  (The first term's second operand is the scratch of the head's
+ * split-K form, which every chunk of up to 16,384 patches runs whatever the knobs; it exceeds the first
+ * only for an HN_SUBCHUNK below half such a chunk.)
  * HN_PIPELINE=1 (opt-in) overlaps a multi-chunk HardNet batch's chunks over a second, internally created
  * stream (forked from and joined back into hip_stream, so graph capture holds) and adds one more
  * chunk x 64 KiB buffer for batches of more than one chunk.
@@ -103,7 +106,12 @@ int hn_workspace_bytes(const hn_model* m, int64_t batch, size_t* bytes_out);
 
 /* d_in: [B,1,32,32] fp32 contiguous (device); d_out: [B,128] fp32 (device).
  * Eval-mode forward of the whole descriptor network (HardNet: input_norm, 7 conv+BN
- * stages, ReLU, L2Norm; NAS: stem, 6 searched blocks, 4x4 head, BN, L2). */
+ * stages, ReLU, L2Norm; NAS: stem, 6 searched blocks, 4x4 head, BN, L2).
+ * Non-finite input: the descriptor of a patch that holds a NaN or an Inf is unspecified (the reference
+ * returns NaN for it; the kernels are built without NaN semantics and may return anything, finite or not).
+ * Such a patch never changes the descriptor of another patch of the batch, and nothing it leaves in the
+ * workspace changes a later call: the forward reads no workspace byte it has not written in the same call,
+ * and writes none outside hn_workspace_bytes nor any output row but its B. */
 int hn_forward(hn_model* m, const float* d_in, int64_t batch, float* d_out,
                void* d_workspace, size_t workspace_bytes, void* hip_stream);
 

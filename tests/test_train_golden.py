@@ -72,6 +72,42 @@ def test_fixture_fp32_reference_gradient_error_is_recorded():
         assert len(errs) == 7 and max(errs.values()) < 2.5e-3
 
 
+def test_train_bucket_fixture_is_complete():
+    """tests/golden/train_buckets.npz (make_train_bucket_golden.py; used by tests/test_gpu_dispatch.py): the
+    inputs regenerate to the recorded hashes and every key of every batch size is there, with its shape."""
+    from fixtures import grad_sample_index, load, N_PROJ
+    from hardnetnas_amd import synth
+    fx = load("train_buckets")
+    meta = fx["meta"]
+    assert meta["batches"] == [640, 1031, 2051]
+    names = [f"g{i}" for i in TRAIN_CONV_IDX] + ["gx"]
+    assert meta["grad_names"] == names
+    sizes = dict(zip(names, (32 * 9, 32 * 32 * 9, 64 * 32 * 9, 64 * 64 * 9, 128 * 64 * 9, 128 * 128 * 9,
+                             128 * 128 * 64, None)))
+    for b in meta["batches"]:
+        mb, pre = meta[f"b{b}"], f"b{b}/"
+        x = synth.synth_patches(b, mb["x_seed"])
+        c = synth.normal(mb["c_seed"], b * 128).astype(np.float32).reshape(b, 128)
+        assert synth.sha256_f32(x) == mb["x_sha256"] and synth.sha256_f32(c) == mb["c_sha256"]
+        rows = fx[pre + "rows"]
+        assert rows.shape == (meta["n_rows"],) and rows[0] == 0 and rows[-1] == b - 1 and (np.diff(rows) > 0).all()
+        assert fx[pre + "y_64"].shape == fx[pre + "y_32"].shape == (meta["n_rows"], 128)
+        assert fx[pre + "y_64"].dtype == np.float64 and fx[pre + "y_32"].dtype == np.float32
+        assert np.abs(np.linalg.norm(fx[pre + "y_64"], axis=1) - 1).max() < 1e-12
+        assert np.abs(fx[pre + "y_32"] - fx[pre + "y_64"]).max() <= 1e-5
+        for i, ch in zip(TRAIN_BN_IDX, (32, 32, 64, 64, 128, 128, 128)):
+            for key in ("rm", "rv"):
+                v = fx[f"{pre}{key}{i}_32"]
+                assert v.shape == (ch,) and v.dtype == np.float32 and np.isfinite(v).all()
+        for k in names:
+            n = sizes[k] or b * 1024
+            assert fx[f"{pre}{k}_sample"].shape == grad_sample_index(n, meta["cap"]).shape
+            assert fx[f"{pre}{k}_proj"].shape == (N_PROJ,) and float(fx[f"{pre}{k}_norm"]) > 0
+        err = fx[pre + "fp32_err"]
+        assert err.shape == (8,) and (err > 0).all() and err.max() < 2.5e-3
+        assert [mb["fp32_grad_l2rel_vs_fp64"][k] for k in names] == list(err)
+
+
 
 # ---- hardnetNAS: the sampled descriptors and the supernet ------------------------------------
 @pytest.mark.parametrize("name", ["wang2", "cov_b"])
