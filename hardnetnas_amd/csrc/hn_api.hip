@@ -52,6 +52,9 @@ void hn_read_knobs(HnKnobs* k) {
   k->c12_abl = env_int("HN_C12_ABL", 0) & 4095;  // (65: k_c12s stamps with P1 on the A-waves)
   k->c12w_pd = env_int("HN_C12W_PD", 11);
   k->dbg = env_int("HN_DEBUG", 0);
+  k->head_abl = env_int("HN_HEAD_ABL", 0);
+  k->w4_abl = env_int("HN_W4_ABL", 0);
+  k->pairdist_abl = env_int("HN_PAIRDIST_ABL", 0);
   k->irf3 = env_int("HN_IRF3", 0) != 0;
 #endif
 }
@@ -257,8 +260,8 @@ struct hn_model {
   // 3 / 4 / 6 / 8 (same-box HardNet 5.25 Mpatches/s at 3 / 3, 5.40 at 6 / 6; conv3 at 8: 10.2 -> 9.9 ms,
   // conv5 flat past 6); conv4: 18 = two patches per stage on the 64-byte swizzled window (15) with the
   // outputs stored by the producer waves; 16 = the direct conv3 / conv5 with epilogue stores through LDS
-  // (the forms before 19)
-  int variant[6] = {6, 0, 5, 26, 18, 21};
+  // (the forms before 19).  hn_create resolves the digits (default 6 0 5 q i l) to the library's builds.
+  const HnConvRow* conv[6] = {};
   size_t ws_floats_per_patch = 0;  // per buffer
   int n_bufs = 0;
   // the chunk pipeline's second stream and events (created on first use; the mutex keeps one call's
@@ -916,25 +919,26 @@ extern "C" int hn_create(const hn_arch_desc* desc, const float* host_params, siz
   if (const char* e = std::getenv("HN_C4_SUB")) m->c4sub = std::max(0, std::atoi(e));
   if (const char* e = std::getenv("HN_NO_IRF")) m->no_irf = std::atoi(e) != 0;
   if (const char* e = std::getenv("HN_NO_IRF2")) m->no_irf2 = std::atoi(e) != 0;
+  int variant[6] = {6, 0, 5, 26, 18, 21};
   if (const char* e = std::getenv("HN_VARIANT")) {
     int i = 0;
     for (const char* c = e; *c && i < 6; ++c)
-      if (*c >= '0' && *c <= '9') m->variant[i++] = *c - '0';
-      else if (*c >= 'a' && *c <= 'z') m->variant[i++] = 10 + (*c - 'a');
+      if (*c >= '0' && *c <= '9') variant[i++] = *c - '0';
+      else if (*c >= 'a' && *c <= 'z') variant[i++] = 10 + (*c - 'a');
   }
   hn_read_knobs(&m->knobs);
   // k_head4 takes 256 patches per workgroup: chunks of 65,536 keep every CU busy in the head
   if (m->knobs.head == 4 && !std::getenv("HN_CHUNK")) m->chunk = 65536;
   for (int l = 0; l < 6; ++l)
-    if (!hn_hardnet_variant_ok(l, m->variant[l])) {
-      const std::string msg = "HN_VARIANT: tiling " + std::to_string(m->variant[l]) +
+    if (!(m->conv[l] = hn_hardnet_conv_row(l, variant[l]))) {
+      const std::string msg = "HN_VARIANT: tiling " + std::to_string(variant[l]) +
                               " is not available for layer " + std::to_string(l);
       delete m;
       return fail(HN_ERR_ARG, msg);
     }
-  if (!hn_c12_cfg_ok(m->knobs.c12_cfg, m->knobs.c12_abl)) {
+  if (!hn_c12_cfg_ok(m->knobs.c12_cfg, m->knobs.c12_abl, m->knobs.c12w_pd)) {
     delete m;
-    return fail(HN_ERR_ARG, "HN_C12_CFG / HN_C12_ABL: no such k_c12 build in this library");
+    return fail(HN_ERR_ARG, "HN_C12_CFG / HN_C12_ABL / HN_C12W_PD: no such k_c12 build in this library");
   }
   if (m->knobs.head < 1 || m->knobs.head > 4) {
     delete m;
@@ -1019,12 +1023,12 @@ static int hardnet_convs(hn_model* m, float* a2, int n, int sub, float* a0, floa
   for (int s0 = 0; s0 < n; s0 += sub) {
     const int ns = std::min(sub, n - s0);
     float* const a2s = a2 + (size_t)s0 * 16384;
-    STAGE("conv3", hn_launch_hardnet_conv(3, m->variant[3], m->hd, a2s, a0, ns, 0.f, st));
+    STAGE("conv3", m->conv[3]->launch(m->hd, a2s, a0, ns, 0.f, st));
     const int c4 = m->c4sub > 0 ? m->c4sub : ns;
     for (int q = 0; q < ns; q += c4)  // (a3 is 16,384 floats per patch, a4 8,192)
-      STAGE("conv4", hn_launch_hardnet_conv(4, m->variant[4], m->hd, a0 + (size_t)q * 16384, a2s + (size_t)q * 8192,
+      STAGE("conv4", m->conv[4]->launch(m->hd, a0 + (size_t)q * 16384, a2s + (size_t)q * 8192,
                                             std::min(c4, ns - q), 0.f, st));
-    STAGE("conv5", hn_launch_hardnet_conv(5, m->variant[5], m->hd, a2s, a5 + (size_t)s0 * 8192, ns, 0.f, st));
+    STAGE("conv5", m->conv[5]->launch(m->hd, a2s, a5 + (size_t)s0 * 8192, ns, 0.f, st));
   }
   return HN_OK;
 }
@@ -1067,15 +1071,15 @@ static int forward_hardnet(hn_model* m, const float* in, int P, int pmax, float*
   } else {
     if (m->unfused_stem) {
       STAGE("stem", hn_launch_stem(in, a0, m->hd.stem_w, m->hd.stem_b, P, ineps >= 0.f, ineps, st));
-      STAGE("conv1", hn_launch_hardnet_conv(1, 0, m->hd, a0, a1, P, 0.f, st));
+      STAGE("conv1", m->conv[1]->launch(m->hd, a0, a1, P, 0.f, st));
     } else {
-      STAGE("stem+conv1", hn_launch_hardnet_conv(0, m->variant[0], m->hd, in, a1, P, ineps, st));
+      STAGE("stem+conv1", m->conv[0]->launch(m->hd, in, a1, P, ineps, st));
     }
-    STAGE("conv2", hn_launch_hardnet_conv(2, m->variant[2], m->hd, a1, a2, P, 0.f, st));
+    STAGE("conv2", m->conv[2]->launch(m->hd, a1, a2, P, 0.f, st));
   }
-  STAGE("conv3", hn_launch_hardnet_conv(3, m->variant[3], m->hd, a2, a1, P, 0.f, st));
-  STAGE("conv4", hn_launch_hardnet_conv(4, m->variant[4], m->hd, a1, a2, P, 0.f, st));
-  STAGE("conv5", hn_launch_hardnet_conv(5, m->variant[5], m->hd, a2, a1, P, 0.f, st));
+  STAGE("conv3", m->conv[3]->launch(m->hd, a2, a1, P, 0.f, st));
+  STAGE("conv4", m->conv[4]->launch(m->hd, a1, a2, P, 0.f, st));
+  STAGE("conv5", m->conv[5]->launch(m->hd, a2, a1, P, 0.f, st));
   STAGE("head", hn_launch_head(a1, out, m->hd.wpack[6], m->hd.bias[6], P, 8192, m->desc.l2_eps, st, false, a2));
   return HN_OK;
 }

@@ -918,149 +918,79 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 }
 #endif  // HN_EXPERIMENTS
 
+// One k_c12 build's launcher.  U8: the build also has the uint8-load instantiations (the production
+// configuration only).
+template <int ABL, int NW, int RB2, int WPE, bool P3I, int WA, bool P2I, int PRIO, bool U8>
+hipError_t c12(const float* in, float* out, const HardnetDev& d, int P, float eps, hipStream_t st, const HnU8In* u8) {
+  if (u8 && !U8) return hipErrorInvalidValue;
+  return hn_with_u8(u8, [&](auto u) {
+    constexpr int U = U8 ? decltype(u)::value : -1;
+    return hn_c12_launch<&k_c12<ABL, NW, RB2, WPE, P3I, WA, P2I, PRIO, U>, &k_c12<0, NW, RB2, WPE, P3I, WA, P2I, PRIO>,
+                         NW * 64>(d.c12_w1, in, out, d, P, eps, st, u8);
+  });
+}
+#ifdef HN_EXPERIMENTS
+hipError_t c12h(const float* in, float* out, const HardnetDev& d, int P, float eps, hipStream_t st, const HnU8In* u8) {
+  return hn_with_u8(u8, [&](auto u) {
+    return hn_c12_launch<&k_c12h<decltype(u)::value>, &k_c12h<-1>, 512>(d.c12_w1, in, out, d, P, eps, st, u8);
+  });
+}
+#endif
+
+// {HN_C12_CFG, HN_C12_ABL, HN_C12W_PD, launcher} of the direct k_c12's builds (hn_internal.h).  12 is the product
+// library's direct-conv1 fallback (the default is 15 = k_c12s, hn_c12w.hip; same-box A/Bs: 12 2-4 % < 7 1.5 % < 2
+// 4.5 % < 0).  The experiments library also has the measured-slower forms <waves, band rows, waves/SIMD, ...>
+// -- (P1, P3) at priority (2, 1) / (1, 2) / (2, 2): within the box noise of 12, removed -- and the timing-only
+// ablation builds of 0, 2 and 12.
+constexpr HnC12Row kC12Rows[] = {
+    {12, 0, kAnyPd, c12<0, 4, 2, 2, false, 2, true, 5, true>},  // 7 with P3 and P1 at priority 1
+#ifdef HN_EXPERIMENTS
+    {0, 0, kAnyPd, c12<0, 8, 4, 2, false, 2, false, 0, false>},  // 8 waves, 4-row bands, 2 waves/SIMD
+    {1, 0, kAnyPd, c12<0, 4, 4, 1, false, 2, false, 0, false>},  // 4, 4, 1 (512-register file)
+    {2, 0, kAnyPd, c12<0, 4, 2, 2, false, 2, false, 0, false>},  // 4 waves, 2-row bands, 2 workgroups/CU
+    // 3 / 4: 0 with tap-interleaved P3, conv2 fragments 2 / 3 taps ahead;  5 / 6: the same for 2
+    {3, 0, kAnyPd, c12<0, 8, 4, 2, true, 2, false, 0, false>},
+    {4, 0, kAnyPd, c12<0, 8, 4, 2, true, 3, false, 0, false>},
+    {5, 0, kAnyPd, c12<0, 4, 2, 2, true, 2, false, 0, false>},
+    {6, 0, kAnyPd, c12<0, 4, 2, 2, true, 3, false, 0, false>},
+    // 7 / 8: 2 / 5 with the tap-interleaved P2 (both halves' chains MFMA by MFMA);  9: 0 with it
+    {7, 0, kAnyPd, c12<0, 4, 2, 2, false, 2, true, 0, false>},
+    {8, 0, kAnyPd, c12<0, 4, 2, 2, true, 2, true, 0, false>},
+    {9, 0, kAnyPd, c12<0, 8, 4, 2, false, 2, true, 0, false>},
+    // 10 / 11: 7 with the P1 wave priority raised to 1 / 3
+    {10, 0, kAnyPd, c12<0, 4, 2, 2, false, 2, true, 1, false>},
+    {11, 0, kAnyPd, c12<0, 4, 2, 2, false, 2, true, 3, false>},
+    {13, 0, kAnyPd, c12h},  // k_c12h (MFMA / helper waves split per SIMD)
+    {0, 1, kAnyPd, c12<1, 8, 4, 2, false, 2, false, 0, false>},
+    {0, 6, kAnyPd, c12<6, 8, 4, 2, false, 2, false, 0, false>},
+    {0, 8, kAnyPd, c12<8, 8, 4, 2, false, 2, false, 0, false>},
+    {2, 6, kAnyPd, c12<6, 4, 2, 2, false, 2, false, 0, false>},
+    {2, 8, kAnyPd, c12<8, 4, 2, 2, false, 2, false, 0, false>},
+    {12, 1, kAnyPd, c12<1, 4, 2, 2, false, 2, true, 5, false>},
+    {12, 6, kAnyPd, c12<6, 4, 2, 2, false, 2, true, 5, false>},
+    {12, 8, kAnyPd, c12<8, 4, 2, 2, false, 2, true, 5, false>},
+    {12, 32, kAnyPd, c12<32, 4, 2, 2, false, 2, true, 5, false>},
+    {12, 64, kAnyPd, c12<64, 4, 2, 2, false, 2, true, 5, false>},
+    {12, 192, kAnyPd, c12<192, 4, 2, 2, false, 2, true, 5, false>},
+#endif
+};
+static_assert(hn_rows_unique(kC12Rows), "one build per (HN_C12_CFG, HN_C12_ABL, HN_C12W_PD)");
+
 }  // namespace
 
-// HN_C12_CFG variants of the direct k_c12 (12 is the product library's direct-conv1 fallback; the default is
-// 15 = k_c12s, hn_c12w.hip).  The experiments library also has the measured-slower forms:
-//   0 <8 waves, 4-row bands, 2 waves/SIMD>   1 <4, 4, 1> (512-register file)
-//   2 <4 waves, 2-row bands, 2 workgroups/CU>
-//   3 / 4: 0 with tap-interleaved P3, conv2 fragments 2 / 3 taps ahead;  5 / 6: the same for 2
-//   7 / 8: 2 / 5 with the tap-interleaved P2 (both halves' chains MFMA by MFMA);  9: 0 with it
-//   10 / 11: 7 with the P1 wave priority raised to 1 / 3;  12: 7 with P3 and P1 at priority 1
-//   13: k_c12h (MFMA / helper waves split per SIMD);  14: k_c12w (conv1 as F(4,3), hn_c12w.hip)
-#ifdef HN_EXPERIMENTS
-#define HN_C12_CFGS(X)                                                                   \
-  X(0, 8, 4, 2, false, 2, false, 0) X(1, 4, 4, 1, false, 2, false, 0) X(2, 4, 2, 2, false, 2, false, 0) \
-  X(3, 8, 4, 2, true, 2, false, 0) X(4, 8, 4, 2, true, 3, false, 0) X(5, 4, 2, 2, true, 2, false, 0)     \
-  X(6, 4, 2, 2, true, 3, false, 0) X(7, 4, 2, 2, false, 2, true, 0) X(8, 4, 2, 2, true, 2, true, 0)      \
-  X(9, 8, 4, 2, false, 2, true, 0) X(10, 4, 2, 2, false, 2, true, 1) X(11, 4, 2, 2, false, 2, true, 3) \
-  X(12, 4, 2, 2, false, 2, true, 5)
-#else
-#define HN_C12_CFGS(X) X(12, 4, 2, 2, false, 2, true, 5)
-#endif  // (P1, P3) at priority (2, 1) / (1, 2) / (2, 2): within the box noise of 12, removed
-
-bool hn_c12_cfg_ok(int cfg, int abl) {
-  if (cfg == kC12Split) {  // k_c12s (hn_c12w.hip)
-#ifdef HN_EXPERIMENTS
-    return abl == 0 || abl == 1 || abl == 2 || abl == 4 || abl == 6 || abl == 64 || abl == 65 || abl == 66 || abl == 72 ||
-           abl == 80 || abl == 84 || abl == 88 || abl == 116 || abl == 86 || abl == 340 || abl == 576 || abl == 1088;
-#else
-    return abl == 0;
-#endif
-  }
-#ifdef HN_EXPERIMENTS
-  if (cfg == kC12Wino)  // k_c12w (hn_c12w.hip)
-    return abl == 0 || abl == 1 || abl == 2 || abl == 4 || abl == 6 || abl == 64 || abl == 192;
-  if (cfg < 0 || cfg > 13) return false;
-#else
-  if (cfg != 12) return false;
-#endif
-  if (!abl) return true;
-#ifdef HN_EXPERIMENTS
-  switch (cfg) {
-    case 0: return abl == 1 || abl == 6 || abl == 8;
-    case 2: return abl == 6 || abl == 8;
-    case 12: return abl == 1 || abl == 6 || abl == 8 || abl == 32 || abl == 64 || abl == 192;
-  }
-#endif
-  return false;
+const HnC12Row* hn_c12_row(int cfg, int abl, int pd) {
+  if (const HnC12Row* r = hn_find_row(kC12Rows, cfg, abl, pd)) return r;
+  return hn_c12w_row(cfg, abl, pd);
 }
+
+bool hn_c12_cfg_ok(int cfg, int abl, int pd) { return hn_c12_row(cfg, abl, pd) != nullptr; }
 
 hipError_t hn_launch_c12(const float* in, float* out, const HardnetDev& d, int P, float eps,
                          hipStream_t st, const HnU8In* u8) {
   if (P <= 0) return hipSuccess;
-  // the calling model's HN_C12_CFG (and, in the HN_EXPERIMENTS library, HN_C12_ABL), hn_create
-  const int cfg = hn_knobs().c12_cfg;  // same-box A/Bs: 12 2-4 % < 7 1.5 % < 2 4.5 % < 0
-  const int abl = hn_knobs().c12_abl;
-  if (!hn_c12_cfg_ok(cfg, abl)) return hipErrorInvalidValue;
-#ifdef HN_EXPERIMENTS
-  if (cfg == kC12Wino) return hn_launch_c12w(in, out, d, P, eps, st, u8, abl);
-#endif
-  if (cfg == kC12Split) return hn_launch_c12s(in, out, d, P, eps, st, u8);
-  if (u8 && ((cfg != 12 && cfg != 13) || abl)) return hipErrorInvalidValue;  // the uint8 loads: production builds only
-  const void* fn = nullptr;
-  int nw = 0;
-  switch (cfg) {
-#define HN_C12_FN(C, W, R, E, I, A, Q, PR)                               \
-  case C:                                                                \
-    fn = reinterpret_cast<const void*>(&k_c12<0, W, R, E, I, A, Q, PR>); \
-    nw = W;                                                              \
-    break;
-    HN_C12_CFGS(HN_C12_FN)
-#undef HN_C12_FN
-#ifdef HN_EXPERIMENTS
-    case 13:
-      fn = reinterpret_cast<const void*>(&k_c12h<-1>);
-      nw = 8;
-      break;
-#endif
-  }
-  if (!fn) return hipErrorInvalidValue;
-  int resident = 0;
-  const hipError_t e = hn_resident_blocks(fn, nw * 64, 0, &resident);
-  if (e != hipSuccess) return e;
-  const int grid = (int)std::min<long>((long)P, resident);
-  const void* src = u8 ? u8->in : static_cast<const void*>(in);
-  const float pm = u8 ? u8->mean : 0.f, ps = u8 ? u8->stdv : 1.f;
-  const int pn = u8 ? u8->normalize : 0;
-#define HN_C12_GO(A, W, R, E, I, WA, Q, PR, ...)                                                 \
-  hipLaunchKernelGGL((k_c12<A, W, R, E, I, WA, Q, PR, ##__VA_ARGS__>), dim3(grid), dim3(W * 64), 0, st, src, \
-                     out, d.stem_w, d.stem_b, static_cast<const uint4*>(d.c12_w1), d.bias[1],   \
-                     static_cast<const uint4*>(d.c12_w2), d.bias[2], P, eps, pm, ps, pn)
-#ifdef HN_EXPERIMENTS
-#define HN_C12H_GO(U)                                                                                        \
-  hipLaunchKernelGGL((k_c12h<U>), dim3(grid), dim3(512), 0, st, src, out, d.stem_w, d.stem_b,               \
-                     static_cast<const uint4*>(d.c12_w1), d.bias[1], static_cast<const uint4*>(d.c12_w2),   \
-                     d.bias[2], P, eps, pm, ps, pn)
-  if (cfg == 13) {
-    if (!u8) HN_C12H_GO(-1);
-    else if (u8->resize == HN_RESIZE_NONE) HN_C12H_GO(HN_RESIZE_NONE);
-    else if (u8->resize == HN_RESIZE_CV2_LINEAR) HN_C12H_GO(HN_RESIZE_CV2_LINEAR);
-    else if (u8->resize == HN_RESIZE_PIL_BILINEAR) HN_C12H_GO(HN_RESIZE_PIL_BILINEAR);
-    else return hipErrorInvalidValue;
-#undef HN_C12H_GO
-    return hipGetLastError();
-  }
-#endif
-  if (u8) {
-    switch (u8->resize) {
-      case HN_RESIZE_NONE: HN_C12_GO(0, 4, 2, 2, false, 2, true, 5, HN_RESIZE_NONE); break;
-      case HN_RESIZE_CV2_LINEAR: HN_C12_GO(0, 4, 2, 2, false, 2, true, 5, HN_RESIZE_CV2_LINEAR); break;
-      case HN_RESIZE_PIL_BILINEAR: HN_C12_GO(0, 4, 2, 2, false, 2, true, 5, HN_RESIZE_PIL_BILINEAR); break;
-      default: return hipErrorInvalidValue;
-    }
-  } else if (abl) {
-#ifdef HN_EXPERIMENTS
-    if (cfg == 0) {
-      switch (abl) {
-        case 1: HN_C12_GO(1, 8, 4, 2, false, 2, false, 0); break;
-        case 6: HN_C12_GO(6, 8, 4, 2, false, 2, false, 0); break;
-        case 8: HN_C12_GO(8, 8, 4, 2, false, 2, false, 0); break;
-      }
-    } else if (cfg == 2) {
-      switch (abl) {
-        case 6: HN_C12_GO(6, 4, 2, 2, false, 2, false, 0); break;
-        case 8: HN_C12_GO(8, 4, 2, 2, false, 2, false, 0); break;
-      }
-    } else if (cfg == 12) {
-      switch (abl) {
-        case 1: HN_C12_GO(1, 4, 2, 2, false, 2, true, 5); break;
-        case 6: HN_C12_GO(6, 4, 2, 2, false, 2, true, 5); break;
-        case 8: HN_C12_GO(8, 4, 2, 2, false, 2, true, 5); break;
-        case 32: HN_C12_GO(32, 4, 2, 2, false, 2, true, 5); break;
-        case 64: HN_C12_GO(64, 4, 2, 2, false, 2, true, 5); break;
-        case 64 + 128: HN_C12_GO(192, 4, 2, 2, false, 2, true, 5); break;
-      }
-    }
-#endif
-  } else {
-    switch (cfg) {
-#define HN_C12_CASE(C, W, R, E, I, A, Q, PR) \
-  case C: HN_C12_GO(0, W, R, E, I, A, Q, PR); break;
-      HN_C12_CFGS(HN_C12_CASE)
-#undef HN_C12_CASE
-    }
-  }
-#undef HN_C12_GO
-  return hipGetLastError();
+  // the calling model's HN_C12_CFG (and, in the HN_EXPERIMENTS library, HN_C12_ABL / HN_C12W_PD), hn_create; the
+  // uint8 loads exist at the default prefetch distances only, whatever HN_C12W_PD
+  const HnKnobs& k = hn_knobs();
+  const HnC12Row* r = hn_c12_row(k.c12_cfg, k.c12_abl, u8 ? 11 : k.c12w_pd);
+  return r ? r->launch(in, out, d, P, eps, st, u8) : hipErrorInvalidValue;
 }

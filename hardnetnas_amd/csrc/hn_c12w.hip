@@ -1036,127 +1036,82 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #undef HN_S_RT
 }
 
+#ifdef HN_EXPERIMENTS
+// One k_c12w build's launcher; the uint8 loads exist for the default build only (U8)
+template <int ABL, int PD2, int PD3, bool U8>
+hipError_t c12w(const float* in, float* out, const HardnetDev& d, int P, float eps, hipStream_t st, const HnU8In* u8) {
+  if (!d.c12_w1w || (u8 && !U8)) return hipErrorInvalidValue;
+  return hn_with_u8(u8, [&](auto u) {
+    constexpr int U = U8 ? decltype(u)::value : -1;
+    return hn_c12_launch<&k_c12w<U, ABL, PD2, PD3>, &k_c12w<-1>, NW * 64>(d.c12_w1w, in, out, d, P, eps, st, u8);
+  });
+}
+#endif
+
+// One k_c12s build's launcher; the uint8 loads exist for the default build only (U8)
+template <int PD2, int PD3, int PRB, int ABL, bool P1A, bool P1I, bool ILV, bool U8>
+hipError_t c12s(const float* in, float* out, const HardnetDev& d, int P, float eps, hipStream_t st, const HnU8In* u8) {
+  if (!d.c12_w1w || (u8 && !U8)) return hipErrorInvalidValue;
+  return hn_with_u8(u8, [&](auto u) {
+    constexpr int U = U8 ? decltype(u)::value : -1;
+    return hn_c12_launch<&k_c12s<U, PD2, PD3, PRB, ABL, P1A, P1I, ILV>, &k_c12s<-1>, 512>(d.c12_w1w, in, out, d, P,
+                                                                                        eps, st, u8);
+  });
+}
+
+// {HN_C12_CFG, HN_C12_ABL, HN_C12W_PD, launcher} of this file's builds (hn_internal.h).  The product library
+// has k_c12s's default build alone; the ablation builds (timing only, wrong results) ignore HN_C12W_PD, but for
+// 84 at 21.
+constexpr HnC12Row kC12wRows[] = {
+    {kC12Split, 0, 11, c12s<1, 1, 1, 0, false, false, false, true>},
+#ifdef HN_EXPERIMENTS
+    // k_c12s by HN_C12W_PD: P2 / P3 B-fragment prefetch distances (tens / units), then other A/Bs
+    {kC12Split, 0, 21, c12s<2, 1, 1, 0, false, false, false, false>},
+    {kC12Split, 0, 22, c12s<2, 2, 1, 0, false, false, false, false>},
+    {kC12Split, 0, 10, c12s<1, 1, 0, 0, false, false, false, false>},  // B-waves at priority 0
+    {kC12Split, 0, 1, c12s<1, 1, 1, 0, true, false, false, false>},    // P1 on the A-waves
+    {kC12Split, 0, 2, c12s<1, 1, 0, 0, true, false, false, false>},    // P1 on the A-waves, B-waves at priority 0
+    {kC12Split, 0, 3, c12s<1, 1, 1, 0, false, true, false, false>},    // P1 split around P3 on the B-waves
+    {kC12Split, 0, 4, c12s<1, 1, 0, 0, false, true, false, false>},    // the same, B-waves at priority 0
+    {kC12Split, 0, 5, c12s<1, 1, 1, 0, false, false, true, false>},    // interleaved MFMA chains
+    {kC12Split, 0, 6, c12s<1, 1, 1, 0, false, true, true, false>},     // + P1 inside P3
+    {kC12Split, 0, 7, c12s<1, 1, 0, 0, false, true, true, false>},     // + B-waves at priority 0
+    // k_c12s by HN_C12_ABL
+    {kC12Split, 1, kAnyPd, c12s<1, 1, 1, 1, false, false, false, false>},
+    {kC12Split, 2, kAnyPd, c12s<1, 1, 1, 2, false, false, false, false>},
+    {kC12Split, 4, kAnyPd, c12s<1, 1, 1, 4, false, false, false, false>},
+    {kC12Split, 6, kAnyPd, c12s<1, 1, 1, 6, false, false, false, false>},
+    {kC12Split, 64, kAnyPd, c12s<1, 1, 1, 64, false, false, false, false>},
+    {kC12Split, 65, kAnyPd, c12s<1, 1, 1, 64, true, false, false, false>},   // stamps with P1 on the A-waves
+    {kC12Split, 66, kAnyPd, c12s<1, 1, 1, 64, false, true, false, false>},
+    {kC12Split, 72, kAnyPd, c12s<1, 1, 1, 64 + 8, false, false, false, false>},   // timing: no P3
+    {kC12Split, 80, kAnyPd, c12s<1, 1, 1, 64 + 16, false, false, false, false>},  // timing: no P1
+    {kC12Split, 88, kAnyPd, c12s<1, 1, 1, 64 + 24, false, false, false, false>},  // timing: neither (P2 alone)
+    {kC12Split, 84, 21, c12s<2, 1, 1, 64 + 20, false, false, false, false>},      // 84 with P2 two steps ahead
+    {kC12Split, 84, kAnyPd, c12s<1, 1, 1, 64 + 20, false, false, false, false>},  // timing: P3 without MFMAs, no P1
+    {kC12Split, 116, kAnyPd, c12s<1, 1, 1, 64 + 20 + 32, false, false, false, false>},  // + P2 without its LDS stream
+    {kC12Split, 340, kAnyPd, c12s<1, 1, 1, 64 + 20, false, false, true, false>},        // 84, interleaved
+    {kC12Split, 86, kAnyPd, c12s<1, 1, 1, 64 + 20 + 2, false, false, false, false>},    // 84 without the conv1 MFMAs
+    {kC12Split, 576, kAnyPd, c12s<1, 1, 1, 64, false, false, true, false>},             // stamps, interleaved
+    {kC12Split, 1088, kAnyPd, c12s<1, 1, 1, 64, false, true, true, false>},             // stamps, interleaved + P1 in P3
+    // k_c12w
+    {kC12Wino, 0, 11, c12w<0, 1, 1, true>},
+    {kC12Wino, 0, 21, c12w<0, 2, 1, false>},
+    {kC12Wino, 0, 31, c12w<0, 3, 1, false>},
+    {kC12Wino, 0, 12, c12w<0, 1, 2, false>},
+    {kC12Wino, 0, 22, c12w<0, 2, 2, false>},
+    {kC12Wino, 0, 32, c12w<0, 3, 2, false>},
+    {kC12Wino, 0, 33, c12w<0, 3, 3, false>},
+    {kC12Wino, 1, kAnyPd, c12w<1, 1, 1, false>},
+    {kC12Wino, 2, kAnyPd, c12w<2, 1, 1, false>},
+    {kC12Wino, 4, kAnyPd, c12w<4, 1, 1, false>},
+    {kC12Wino, 6, kAnyPd, c12w<6, 1, 1, false>},
+    {kC12Wino, 64, kAnyPd, c12w<64, 1, 1, false>},
+    {kC12Wino, 192, kAnyPd, c12w<192, 1, 1, false>},
+#endif
+};
+static_assert(hn_rows_unique(kC12wRows), "one build per (HN_C12_CFG, HN_C12_ABL, HN_C12W_PD)");
+
 }  // namespace
 
-#ifdef HN_EXPERIMENTS
-hipError_t hn_launch_c12w(const float* in, float* out, const HardnetDev& d, int P, float eps, hipStream_t st,
-                          const HnU8In* u8, int abl) {
-  if (P <= 0) return hipSuccess;
-  if (!d.c12_w1w) return hipErrorInvalidValue;
-  int resident = 0;
-  const hipError_t e = hn_resident_blocks(reinterpret_cast<const void*>(&k_c12w<-1>), NW * 64, 0, &resident);
-  if (e != hipSuccess) return e;
-  const int grid = (int)std::min<long>((long)P, resident);
-  const void* src = u8 ? u8->in : static_cast<const void*>(in);
-  const float pm = u8 ? u8->mean : 0.f, ps = u8 ? u8->stdv : 1.f;
-  const int pn = u8 ? u8->normalize : 0;
-#define HN_C12W_GO(U, ...)                                                                                \
-  hipLaunchKernelGGL((k_c12w<U, ##__VA_ARGS__>), dim3(grid), dim3(NW * 64), 0, st, src, out, d.stem_w, d.stem_b,        \
-                     static_cast<const uint4*>(d.c12_w1w), d.bias[1], static_cast<const uint4*>(d.c12_w2), \
-                     d.bias[2], P, eps, pm, ps, pn)
-  const int pd = hn_knobs().c12w_pd;
-  if (!u8 && !abl && pd != 11) {
-    switch (pd) {
-      case 21: HN_C12W_GO(-1, 0, 2, 1); break;
-      case 31: HN_C12W_GO(-1, 0, 3, 1); break;
-      case 12: HN_C12W_GO(-1, 0, 1, 2); break;
-      case 22: HN_C12W_GO(-1, 0, 2, 2); break;
-      case 32: HN_C12W_GO(-1, 0, 3, 2); break;
-      case 33: HN_C12W_GO(-1, 0, 3, 3); break;
-      default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-  }
-  if (abl) {
-#ifdef HN_EXPERIMENTS
-    if (u8) return hipErrorInvalidValue;
-    switch (abl) {
-      case 1: HN_C12W_GO(-1, 1); break;
-      case 2: HN_C12W_GO(-1, 2); break;
-      case 4: HN_C12W_GO(-1, 4); break;
-      case 6: HN_C12W_GO(-1, 6); break;
-      case 64: HN_C12W_GO(-1, 64); break;
-      case 192: HN_C12W_GO(-1, 192); break;
-      default: return hipErrorInvalidValue;
-    }
-#else
-    return hipErrorInvalidValue;
-#endif
-  } else if (!u8) HN_C12W_GO(-1);
-  else if (u8->resize == HN_RESIZE_NONE) HN_C12W_GO(HN_RESIZE_NONE);
-  else if (u8->resize == HN_RESIZE_CV2_LINEAR) HN_C12W_GO(HN_RESIZE_CV2_LINEAR);
-  else if (u8->resize == HN_RESIZE_PIL_BILINEAR) HN_C12W_GO(HN_RESIZE_PIL_BILINEAR);
-  else return hipErrorInvalidValue;
-#undef HN_C12W_GO
-  return hipGetLastError();
-}
-
-#endif  // HN_EXPERIMENTS
-
-hipError_t hn_launch_c12s(const float* in, float* out, const HardnetDev& d, int P, float eps, hipStream_t st,
-                          const HnU8In* u8) {
-  if (P <= 0) return hipSuccess;
-  if (!d.c12_w1w) return hipErrorInvalidValue;
-  int resident = 0;
-  const hipError_t e = hn_resident_blocks(reinterpret_cast<const void*>(&k_c12s<-1>), 512, 0, &resident);
-  if (e != hipSuccess) return e;
-  const int grid = (int)std::min<long>((long)P, resident);
-  const void* src = u8 ? u8->in : static_cast<const void*>(in);
-  const float pm = u8 ? u8->mean : 0.f, ps = u8 ? u8->stdv : 1.f;
-  const int pn = u8 ? u8->normalize : 0;
-#define HN_C12S_GO(U, ...)                                                                                \
-  hipLaunchKernelGGL((k_c12s<U, ##__VA_ARGS__>), dim3(grid), dim3(512), 0, st, src, out, d.stem_w, d.stem_b, \
-                     static_cast<const uint4*>(d.c12_w1w), d.bias[1], static_cast<const uint4*>(d.c12_w2),   \
-                     d.bias[2], P, eps, pm, ps, pn)
-#ifdef HN_EXPERIMENTS
-  const int pd = hn_knobs().c12w_pd;
-  const int abl = hn_knobs().c12_abl + (hn_knobs().c12w_pd == 21 && hn_knobs().c12_abl == 84 ? 1000 : 0);
-  if (abl) {
-    if (u8) return hipErrorInvalidValue;
-    switch (abl) {
-      case 1: HN_C12S_GO(-1, 1, 1, 1, 1); break;
-      case 2: HN_C12S_GO(-1, 1, 1, 1, 2); break;
-      case 4: HN_C12S_GO(-1, 1, 1, 1, 4); break;
-      case 6: HN_C12S_GO(-1, 1, 1, 1, 6); break;
-      case 64: HN_C12S_GO(-1, 1, 1, 1, 64); break;
-      case 65: HN_C12S_GO(-1, 1, 1, 1, 64, true); break;
-      case 66: HN_C12S_GO(-1, 1, 1, 1, 64, false, true); break;
-      case 64 + 8: HN_C12S_GO(-1, 1, 1, 1, 64 + 8); break;    // timing: no P3
-      case 64 + 16: HN_C12S_GO(-1, 1, 1, 1, 64 + 16); break;  // timing: no P1
-      case 64 + 24: HN_C12S_GO(-1, 1, 1, 1, 64 + 24); break;  // timing: neither (P2 alone)
-      case 64 + 20: HN_C12S_GO(-1, 1, 1, 1, 64 + 20); break;  // timing: P3 without MFMAs, no P1
-      case 64 + 20 + 32: HN_C12S_GO(-1, 1, 1, 1, 64 + 20 + 32); break;  // + P2 without its LDS stream
-      case 64 + 20 + 256: HN_C12S_GO(-1, 1, 1, 1, 64 + 20, false, false, true); break;  // 84, interleaved
-      case 64 + 20 + 2: HN_C12S_GO(-1, 1, 1, 1, 64 + 20 + 2); break;  // 84 without the conv1 MFMAs
-      case 64 + 512: HN_C12S_GO(-1, 1, 1, 1, 64, false, false, true); break;  // stamps, interleaved
-      case 64 + 1024: HN_C12S_GO(-1, 1, 1, 1, 64, false, true, true); break;  // stamps, interleaved + P1 in P3
-      case 64 + 20 + 1000: HN_C12S_GO(-1, 2, 1, 1, 64 + 20); break;  // the same, P2 two steps ahead
-      default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-  }
-  if (!u8 && pd != 11) {
-    switch (pd) {
-      case 21: HN_C12S_GO(-1, 2, 1); break;
-      case 22: HN_C12S_GO(-1, 2, 2); break;
-      case 10: HN_C12S_GO(-1, 1, 1, 0); break;  // B-waves at priority 0
-      case 1: HN_C12S_GO(-1, 1, 1, 1, 0, true); break;  // P1 on the A-waves
-      case 2: HN_C12S_GO(-1, 1, 1, 0, 0, true); break;  // P1 on the A-waves, B-waves at priority 0
-      case 3: HN_C12S_GO(-1, 1, 1, 1, 0, false, true); break;  // P1 split around P3 on the B-waves
-      case 4: HN_C12S_GO(-1, 1, 1, 0, 0, false, true); break;  // the same, B-waves at priority 0
-      case 5: HN_C12S_GO(-1, 1, 1, 1, 0, false, false, true); break;  // interleaved MFMA chains
-      case 6: HN_C12S_GO(-1, 1, 1, 1, 0, false, true, true); break;   // + P1 inside P3
-      case 7: HN_C12S_GO(-1, 1, 1, 0, 0, false, true, true); break;   // + B-waves at priority 0
-      default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-  }
-#endif  // HN_EXPERIMENTS
-  if (!u8) HN_C12S_GO(-1);
-  else if (u8->resize == HN_RESIZE_NONE) HN_C12S_GO(HN_RESIZE_NONE);
-  else if (u8->resize == HN_RESIZE_CV2_LINEAR) HN_C12S_GO(HN_RESIZE_CV2_LINEAR);
-  else if (u8->resize == HN_RESIZE_PIL_BILINEAR) HN_C12S_GO(HN_RESIZE_PIL_BILINEAR);
-  else return hipErrorInvalidValue;
-#undef HN_C12S_GO
-  return hipGetLastError();
-}
+const HnC12Row* hn_c12w_row(int cfg, int abl, int pd) { return hn_find_row(kC12wRows, cfg, abl, pd); }

@@ -1787,176 +1787,162 @@ __global__ __launch_bounds__(512) void k_head4(const float* __restrict__ a, floa
 // ------------------------------------------------------------------------------------
 // host launchers
 // ------------------------------------------------------------------------------------
-// stem-fused kernels carry the normalised patch (34x34 fp32) + 8 reduction floats
-template <class CFG, bool STEM>
-constexpr int conv_lds() { return CFG::LDS + (STEM ? (34 * 34 + 8) * 4 : 0); }
+namespace {
 
-#define HN_CONV(NAME, STEM, CIN, COUT, HIN, S, NP, TR, WM, WN)                             \
-  using NAME##_cfg = ConvCfg<CIN, COUT, HIN, S, NP, TR, WM, WN>;                           \
-  static hipError_t NAME##_lo(const float* in, float* out, const void* wp, const float* bias,\
-                         int P, const float* sw, const float* sb, float eps,               \
-                         hipStream_t st, float lo) {                                       \
-    constexpr int lds = conv_lds<NAME##_cfg, STEM>();                                      \
-    int resident = 0; /* sets the dynamic-LDS limit on this device */                     \
-    hipError_t e = hn_resident_blocks(                                                     \
-        reinterpret_cast<const void*>(&k_conv3x3<CIN, COUT, HIN, S, NP, TR, WM, WN, STEM>), \
-        256, lds, &resident);                                                              \
-    if (e != hipSuccess) return e;                                                         \
-    const int grid = (P + NP - 1) / NP * NAME##_cfg::RT;                                   \
-    hipLaunchKernelGGL((k_conv3x3<CIN, COUT, HIN, S, NP, TR, WM, WN, STEM>), dim3(grid),   \
-                       dim3(256), lds, st, in, out, static_cast<const uint4*>(wp), bias, P, \
-                       sw, sb, eps, hn_knobs().dbg, lo);                                   \
-    return hipGetLastError();                                                              \
-  }                                                                                        \
-  static hipError_t NAME(const float* in, float* out, const void* wp, const float* bias,   \
-                         int P, const float* sw, const float* sb, float eps, hipStream_t st) { \
-    return NAME##_lo(in, out, wp, bias, P, sw, sb, eps, st, 0.f);                          \
-  }
+// A build of one of the three conv kernels: the instantiation, its Cfg, the patches per tile and whether it
+// fuses the stem.  The aliases spell every template argument of the kernel out.
+template <auto Kernel, class Cfg_, int NP_, bool STEM_, bool PERSISTENT_>
+struct ConvBuild {
+  static constexpr auto kernel = Kernel;
+  using Cfg = Cfg_;
+  static constexpr int NP = NP_;
+  static constexpr bool STEM = STEM_, PERSISTENT = PERSISTENT_;
+};
+template <int CIN, int COUT, int HIN, int S, int NP, int TR, int WM, int WN, bool STEM>
+using Direct = ConvBuild<&k_conv3x3<CIN, COUT, HIN, S, NP, TR, WM, WN, STEM>, ConvCfg<CIN, COUT, HIN, S, NP, TR, WM, WN>,
+                         NP, STEM, false>;
+template <int CIN, int COUT, int HIN, int S, int NP, int TR, int WM, int WN, bool STEM, int ABL, bool CST>
+using Pipe = ConvBuild<&k_conv_pipe<CIN, COUT, HIN, S, NP, TR, WM, WN, STEM, ABL, CST>,
+                       PipeCfg<CIN, COUT, HIN, S, NP, TR, WM, WN, STEM, CST>, NP, STEM, true>;
+template <int CIN, int COUT, int HIN, int S, int NP, int TR, int WM, int WN, bool STEM, int ABL, int PX, bool CST,
+          bool PST>
+using Ws = ConvBuild<&k_conv_ws<CIN, COUT, HIN, S, NP, TR, WM, WN, STEM, ABL, PX, CST, PST>,
+                     WsCfg<CIN, COUT, HIN, S, NP, TR, WM, WN, STEM, PX, CST, PST>, NP, STEM, true>;
 
-// variant 0 = default tiling; variant 1 = smaller LDS footprint / more workgroups per CU
-HN_CONV(conv1s_launch, true, 32, 32, 32, 1, 1, 8, 4, 1)
-#ifdef HN_EXPERIMENTS  // superseded tiling (experiments library only)
-HN_CONV(conv1s_v1, true, 32, 32, 32, 1, 1, 4, 4, 1)
-#endif
-HN_CONV(conv1_launch, false, 32, 32, 32, 1, 1, 8, 4, 1)
-HN_CONV(conv2_launch, false, 32, 64, 32, 2, 1, 8, 2, 2)
-#ifdef HN_EXPERIMENTS  // superseded tiling (experiments library only)
-HN_CONV(conv2_v1, false, 32, 64, 32, 2, 1, 4, 2, 2)
-#endif
-HN_CONV(conv3_launch, false, 64, 64, 16, 1, 1, 16, 2, 2)
-#ifdef HN_EXPERIMENTS  // superseded tiling (experiments library only)
-HN_CONV(conv3_v1, false, 64, 64, 16, 1, 1, 8, 2, 2)
-#endif
-HN_CONV(conv4_launch, false, 64, 128, 16, 2, 1, 8, 1, 4)
-#ifdef HN_EXPERIMENTS  // superseded tiling (experiments library only)
-HN_CONV(conv4_v1, false, 64, 128, 16, 2, 1, 4, 1, 4)
-#endif
-HN_CONV(conv5_launch, false, 128, 128, 8, 1, 2, 8, 1, 4)
-#ifdef HN_EXPERIMENTS  // superseded tiling (experiments library only)
-HN_CONV(conv5_v1, false, 128, 128, 8, 1, 1, 8, 1, 4)
-#endif
+// k_conv3x3: one workgroup per tile; stem-fused builds carry the normalised patch (34x34 fp32) + 8 reduction floats
+template <class B>
+hipError_t launch_direct(int tiles, const float* in, float* out, const uint4* wp, const float* bias, int P,
+                         const float* sw, const float* sb, float eps, hipStream_t st, float lo) {
+  constexpr int lds = B::Cfg::LDS + (B::STEM ? (34 * 34 + 8) * 4 : 0);
+  int resident = 0;  // sets the dynamic-LDS limit on this device
+  const hipError_t e = hn_resident_blocks(reinterpret_cast<const void*>(B::kernel), 256, lds, &resident);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(B::kernel, dim3(tiles), dim3(256), lds, st, in, out, wp, bias, P, sw, sb, eps, hn_knobs().dbg, lo);
+  return hipGetLastError();
+}
 
-// persistent launch: grid = min(tiles, resident workgroups) (occupancy query, cached)
-#define HN_PIPE(NAME, STEM, CIN, COUT, HIN, S, NP, TR, WM, WN) HN_PIPE_A(NAME, STEM, CIN, COUT, HIN, S, NP, TR, WM, WN, 0)
-#define HN_PIPE_A(NAME, STEM, CIN, COUT, HIN, S, NP, TR, WM, WN, ABL) HN_PIPE_C(NAME, STEM, CIN, COUT, HIN, S, NP, TR, WM, WN, ABL, false)
-#define HN_PIPE_C(NAME, STEM, CIN, COUT, HIN, S, NP, TR, WM, WN, ABL, CST)                 \
-  using NAME##_cfg = PipeCfg<CIN, COUT, HIN, S, NP, TR, WM, WN, STEM, CST>;                \
-  static hipError_t NAME##_lo(const float* in, float* out, const void* wp, const float* bias,\
-                         int P, const float* sw, const float* sb, float eps,               \
-                         hipStream_t st, float lo) {                                       \
-    constexpr int lds = NAME##_cfg::SMEM;                                                  \
-    const void* fn = reinterpret_cast<const void*>(                                        \
-        &k_conv_pipe<CIN, COUT, HIN, S, NP, TR, WM, WN, STEM, ABL, CST>);                       \
-    int resident = 0;                                                                      \
-    const hipError_t e = hn_resident_blocks(fn, NAME##_cfg::NTHR, lds, &resident);         \
-    if (e != hipSuccess) return e;                                                         \
-    const int tiles = (P + NP - 1) / NP * NAME##_cfg::RT;                                  \
-    const int grid = std::min(tiles, resident);                                            \
-    hipLaunchKernelGGL((k_conv_pipe<CIN, COUT, HIN, S, NP, TR, WM, WN, STEM, ABL, CST>), dim3(grid), \
-                       dim3(NAME##_cfg::NTHR), lds, st, in, out,                           \
-                       static_cast<const uint4*>(wp), bias, P, sw, sb, eps, lo);               \
-    return hipGetLastError();                                                              \
-  }                                                                                        \
-  static hipError_t NAME(const float* in, float* out, const void* wp, const float* bias,   \
-                         int P, const float* sw, const float* sb, float eps, hipStream_t st) { \
-    return NAME##_lo(in, out, wp, bias, P, sw, sb, eps, st, 0.f);                          \
-  }
+// lo: the ReLU floor (0; -INFINITY for the train mode's plain convolutions, hn_launch_conv_raw)
+template <class B>
+hipError_t conv_launch(const float* in, float* out, const void* wp, const float* bias, int P, const float* sw,
+                       const float* sb, float eps, hipStream_t st, float lo) {
+  using C = typename B::Cfg;
+  const int tiles = (P + B::NP - 1) / B::NP * C::RT;
+  const uint4* w = static_cast<const uint4*>(wp);
+  if constexpr (B::PERSISTENT)
+    return hn_launch_persistent<B::kernel, C::NTHR, C::SMEM>(tiles, st, in, out, w, bias, P, sw, sb, eps, lo);
+  else
+    return launch_direct<B>(tiles, in, out, w, bias, P, sw, sb, eps, st, lo);
+}
 
-#ifdef HN_EXPERIMENTS  // superseded tiling (experiments library only)
-HN_PIPE(pipe1s, true, 32, 32, 32, 1, 1, 4, 4, 1)
-HN_PIPE(pipe1s_t8, true, 32, 32, 32, 1, 1, 8, 4, 1)
-HN_PIPE(pipe2, false, 32, 64, 32, 2, 1, 4, 2, 2)
-HN_PIPE(pipe2_t2, false, 32, 64, 32, 2, 1, 2, 1, 2)
-HN_PIPE(pipe3, false, 64, 64, 16, 1, 1, 8, 2, 2)
-HN_PIPE(pipe3_t16, false, 64, 64, 16, 1, 1, 16, 2, 2)
-HN_PIPE(pipe4, false, 64, 128, 16, 2, 1, 4, 1, 4)
-HN_PIPE(pipe4_t8, false, 64, 128, 16, 2, 1, 8, 1, 4)
-HN_PIPE(pipe5, false, 128, 128, 8, 1, 1, 8, 1, 4)
-HN_PIPE(pipe5_np2, false, 128, 128, 8, 1, 2, 8, 1, 4)
-#endif
-HN_PIPE_C(pipe5_cst, false, 128, 128, 8, 1, 2, 8, 1, 4, 0, true)  // HN_VARIANT digit g at conv5
+// A table row's launcher: conv layer L's weights (the stem's and conv1's for a stem-fused build)
+template <int L, class B>
+hipError_t row(const HardnetDev& d, const float* in, float* out, int P, float eps, hipStream_t st) {
+  static_assert(B::STEM == (L == 0), "layer 0 is the stem-fused conv1");
+  if constexpr (B::STEM)
+    return conv_launch<B>(in, out, d.wpack[1], d.bias[1], P, d.stem_w, d.stem_b, eps, st, 0.f);
+  else
+    return conv_launch<B>(in, out, d.wpack[L], d.bias[L], P, nullptr, nullptr, 0.f, st, 0.f);
+}
 
-#define HN_WS(NAME, CIN, COUT, HIN, S, NP, TR, WM, WN) HN_WS_S(NAME, false, CIN, COUT, HIN, S, NP, TR, WM, WN)
-#define HN_WS_S(NAME, STEM, CIN, COUT, HIN, S, NP, TR, WM, WN) HN_WS_A(NAME, STEM, CIN, COUT, HIN, S, NP, TR, WM, WN, 0)
-#define HN_WS_A(NAME, STEM, CIN, COUT, HIN, S, NP, TR, WM, WN, ABL) HN_WS_X(NAME, STEM, CIN, COUT, HIN, S, NP, TR, WM, WN, ABL, 80)
-#define HN_WS_X(NAME, STEM, CIN, COUT, HIN, S, NP, TR, WM, WN, ABL, PX) HN_WS_C(NAME, STEM, CIN, COUT, HIN, S, NP, TR, WM, WN, ABL, PX, false)
-#define HN_WS_C(NAME, STEM, CIN, COUT, HIN, S, NP, TR, WM, WN, ABL, PX, CST) \
-  HN_WS_P(NAME, STEM, CIN, COUT, HIN, S, NP, TR, WM, WN, ABL, PX, CST, false)
-#define HN_WS_P(NAME, STEM, CIN, COUT, HIN, S, NP, TR, WM, WN, ABL, PX, CST, PST)        \
-  using NAME##_cfg = WsCfg<CIN, COUT, HIN, S, NP, TR, WM, WN, STEM, PX, CST, PST>;              \
-  static hipError_t NAME##_lo(const float* in, float* out, const void* wp, const float* bias,\
-                         int P, const float* sw, const float* sb, float eps, hipStream_t st, \
-                         float lo) {                                                       \
-    constexpr int lds = NAME##_cfg::SMEM;                                                  \
-    const void* fn =                                                                       \
-        reinterpret_cast<const void*>(&k_conv_ws<CIN, COUT, HIN, S, NP, TR, WM, WN, STEM, ABL, PX, CST, PST>); \
-    int resident = 0;                                                                      \
-    const hipError_t e = hn_resident_blocks(fn, NAME##_cfg::NTHR, lds, &resident);         \
-    if (e != hipSuccess) return e;                                                         \
-    const int tiles = (P + NP - 1) / NP * NAME##_cfg::RT;                                  \
-    const int grid = std::min(tiles, resident);                                            \
-    hipLaunchKernelGGL((k_conv_ws<CIN, COUT, HIN, S, NP, TR, WM, WN, STEM, ABL, PX, CST, PST>), dim3(grid), \
-                       dim3(NAME##_cfg::NTHR), lds, st, in, out,                           \
-                       static_cast<const uint4*>(wp), bias, P, sw, sb, eps, lo);               \
-    return hipGetLastError();                                                              \
-  }                                                                                        \
-  static hipError_t NAME(const float* in, float* out, const void* wp, const float* bias,   \
-                         int P, const float* sw, const float* sb, float eps, hipStream_t st) { \
-    return NAME##_lo(in, out, wp, bias, P, sw, sb, eps, st, 0.f);                          \
-  }
+// The product library's builds (Conv1, Ws2, Ws3Cst, Ws4Np2 and Pipe5Cst are also the train mode's,
+// hn_launch_conv_raw; Conv1..Conv5 hn_conv_lds_bytes').  The kernels are emitted in the order they are first
+// named: keep this one and the product code object stays byte for byte the same.
+using Conv1s = Direct<32, 32, 32, 1, 1, 8, 4, 1, true>;
+using Conv1 = Direct<32, 32, 32, 1, 1, 8, 4, 1, false>;
+using Conv2 = Direct<32, 64, 32, 2, 1, 8, 2, 2, false>;
+using Conv3 = Direct<64, 64, 16, 1, 1, 16, 2, 2, false>;
+using Conv4 = Direct<64, 128, 16, 2, 1, 8, 1, 4, false>;
+using Conv5 = Direct<128, 128, 8, 1, 2, 8, 1, 4, false>;
+using Pipe5Cst = Pipe<128, 128, 8, 1, 2, 8, 1, 4, false, 0, true>;
+using Ws1s = Ws<32, 32, 32, 1, 1, 4, 4, 1, true, 0, 80, false, false>;
+using Ws1sT8 = Ws<32, 32, 32, 1, 1, 8, 4, 1, true, 0, 80, false, false>;
+using Ws2 = Ws<32, 64, 32, 2, 1, 4, 2, 2, false, 0, 80, false, false>;
+using Ws2T2 = Ws<32, 64, 32, 2, 1, 2, 1, 2, false, 0, 80, false, false>;
+// conv4 on the 64-byte swizzled window, two patches per stage, 2 x 2 waves; Pst: the same with the outputs
+// stored by the producer waves
+using Ws4Np2 = Ws<64, 128, 16, 2, 2, 8, 2, 2, false, 0, 64, false, false>;
+using Ws4Pst = Ws<64, 128, 16, 2, 2, 8, 2, 2, false, 0, 64, false, true>;
+// conv3 with the epilogue transposed through LDS for whole-row stores (CST; conv3 12.8 -> 12.1 ms).  The same on
+// conv4's one-patch tiling (8.49 -> 8.35 ms) and conv5's k_conv_ws form (13.0 -> 12.6) stays behind their
+// defaults; conv5's k_conv_pipe gets the half-tile form (Pipe5Cst, 11.9 -> 11.5 ms).
+using Ws3Cst = Ws<64, 64, 16, 1, 1, 16, 2, 2, false, 0, 80, true, false>;
 
-HN_WS_S(ws1s, true, 32, 32, 32, 1, 1, 4, 4, 1)
-HN_WS_S(ws1s_t8, true, 32, 32, 32, 1, 1, 8, 4, 1)
-HN_WS(ws2, 32, 64, 32, 2, 1, 4, 2, 2)
-HN_WS(ws2_t2, 32, 64, 32, 2, 1, 2, 1, 2)
-#ifdef HN_EXPERIMENTS  // conv3..conv5's generic warp-specialised tilings, superseded by their defaults
-HN_WS(ws3, 64, 64, 16, 1, 1, 8, 2, 2)
-HN_WS(ws3_t16, 64, 64, 16, 1, 1, 16, 2, 2)
-HN_WS(ws4, 64, 128, 16, 2, 1, 4, 1, 4)
-HN_WS(ws4_t8, 64, 128, 16, 2, 1, 8, 1, 4)
-HN_WS(ws5, 128, 128, 8, 1, 1, 8, 1, 4)
-HN_WS(ws5_np2, 128, 128, 8, 1, 2, 8, 1, 4)
-#endif
-// conv4 with the 64-byte swizzled window: two patches per stage (twice the weight reuse of ws4_t8)
-// -- HN_VARIANT digit d -- and the same layout at one patch (digit e)
-#ifdef HN_EXPERIMENTS  // superseded tiling (experiments library only)
-HN_WS_X(ws4_np2s, false, 64, 128, 16, 2, 2, 8, 1, 4, 0, 64)
-HN_WS_X(ws4_s, false, 64, 128, 16, 2, 1, 8, 1, 4, 0, 64)
-#endif
-HN_WS_X(ws4_np2s22, false, 64, 128, 16, 2, 2, 8, 2, 2, 0, 64)  // digit f: 2 x 2 waves
-// digit i: the same with the outputs stored by the producer waves (PST)
-HN_WS_P(ws4_pst, false, 64, 128, 16, 2, 2, 8, 2, 2, 0, 64, false, true)
-// conv3 with the epilogue transposed through LDS for whole-row stores (CST): HN_VARIANT digit g
-// (the default, conv3 12.8 -> 12.1 ms).  The same on conv4's one-patch tiling (8.49 -> 8.35 ms)
-// and conv5's k_conv_ws form (13.0 -> 12.6) stays behind their defaults; conv5's k_conv_pipe
-// gets the half-tile form (pipe5_cst, 11.9 -> 11.5 ms, the default).
-HN_WS_C(ws3_cst, false, 64, 64, 16, 1, 1, 16, 2, 2, 0, 80, true)
+// Every build of this file's kernels: {layer, HN_VARIANT digit, launcher}.  The product library has the defaults
+// (digits 6 0 5 q i l; q and l are hn_wino1.hip's) and one fallback per stage -- 0 (k_conv3x3) everywhere, 5 / 6
+// (warp-specialised, smaller / larger tile) for the HN_NO_C12 stem+conv1 and conv2, f (conv4 with the MFMA
+// waves' own stores), g (direct conv3 / conv5 with epilogue stores through LDS).  The measured-slower tilings
+// and the timing-only ablation builds (wrong results) exist only with -DHN_EXPERIMENTS.
+constexpr HnConvRow kConvRows[] = {
+    {0, 0, row<0, Conv1s>},
+    {0, 5, row<0, Ws1s>},
+    {0, 6, row<0, Ws1sT8>},
+    // conv1 alone (HN_UNFUSED_STEM) has one build: the accepted digits all select it
+    {1, 0, row<1, Conv1>},
+    {1, 5, row<1, Conv1>},
+    {1, 6, row<1, Conv1>},
+    {2, 0, row<2, Conv2>},
+    {2, 5, row<2, Ws2>},
+    {2, 6, row<2, Ws2T2>},
+    {3, 0, row<3, Conv3>},
+    {3, 16, row<3, Ws3Cst>},  // g
+    {4, 0, row<4, Conv4>},
+    {4, 15, row<4, Ws4Np2>},  // f
+    {4, 18, row<4, Ws4Pst>},  // i
+    {5, 0, row<5, Conv5>},
+    {5, 16, row<5, Pipe5Cst>},  // g
 #ifdef HN_EXPERIMENTS
-// conv3 with the outputs stored by the producer waves (PST, HN_VARIANT digit i): 12.8 vs 12.1 ms
-// for the CST form (same-box A/B; the DEEP producers' two extra barriers per tile cost more than
-// the MFMA waves' whole-row stores)
-HN_WS_P(ws3_pst, false, 64, 64, 16, 1, 1, 16, 2, 2, 0, 80, false, true)
+    // 1: k_conv3x3 with the smaller LDS footprint / more workgroups per CU
+    {0, 1, row<0, Direct<32, 32, 32, 1, 1, 4, 4, 1, true>>},
+    {2, 1, row<2, Direct<32, 64, 32, 2, 1, 4, 2, 2, false>>},
+    {3, 1, row<3, Direct<64, 64, 16, 1, 1, 8, 2, 2, false>>},
+    {4, 1, row<4, Direct<64, 128, 16, 2, 1, 4, 1, 4, false>>},
+    {5, 1, row<5, Direct<128, 128, 8, 1, 1, 8, 1, 4, false>>},
+    // 2 / 3: k_conv_pipe, smaller / larger tile
+    {0, 2, row<0, Pipe<32, 32, 32, 1, 1, 4, 4, 1, true, 0, false>>},
+    {0, 3, row<0, Pipe<32, 32, 32, 1, 1, 8, 4, 1, true, 0, false>>},
+    {2, 2, row<2, Pipe<32, 64, 32, 2, 1, 2, 1, 2, false, 0, false>>},
+    {2, 3, row<2, Pipe<32, 64, 32, 2, 1, 4, 2, 2, false, 0, false>>},
+    {3, 2, row<3, Pipe<64, 64, 16, 1, 1, 8, 2, 2, false, 0, false>>},
+    {3, 3, row<3, Pipe<64, 64, 16, 1, 1, 16, 2, 2, false, 0, false>>},
+    {4, 2, row<4, Pipe<64, 128, 16, 2, 1, 4, 1, 4, false, 0, false>>},
+    {4, 3, row<4, Pipe<64, 128, 16, 2, 1, 8, 1, 4, false, 0, false>>},
+    {5, 2, row<5, Pipe<128, 128, 8, 1, 1, 8, 1, 4, false, 0, false>>},
+    {5, 3, row<5, Pipe<128, 128, 8, 1, 2, 8, 1, 4, false, 0, false>>},
+    {1, 1, row<1, Conv1>},
+    {1, 2, row<1, Conv1>},
+    {1, 3, row<1, Conv1>},
+    // 5 / 6 on conv3..conv5: the generic warp-specialised tilings, superseded by their defaults
+    {3, 5, row<3, Ws<64, 64, 16, 1, 1, 8, 2, 2, false, 0, 80, false, false>>},
+    {3, 6, row<3, Ws<64, 64, 16, 1, 1, 16, 2, 2, false, 0, 80, false, false>>},
+    {4, 5, row<4, Ws<64, 128, 16, 2, 1, 4, 1, 4, false, 0, 80, false, false>>},
+    {4, 6, row<4, Ws<64, 128, 16, 2, 1, 8, 1, 4, false, 0, 80, false, false>>},
+    {5, 5, row<5, Ws<128, 128, 8, 1, 1, 8, 1, 4, false, 0, 80, false, false>>},
+    {5, 6, row<5, Ws<128, 128, 8, 1, 2, 8, 1, 4, false, 0, 80, false, false>>},
+    // 7: wider N tiles (fewer A-fragment reads, weights shared through L1)
+    {3, 7, row<3, Ws<64, 64, 16, 1, 1, 16, 4, 1, false, 0, 80, false, false>>},
+    {4, 7, row<4, Ws<64, 128, 16, 2, 1, 8, 2, 2, false, 0, 80, false, false>>},
+    {5, 7, row<5, Ws<128, 128, 8, 1, 2, 8, 2, 2, false, 0, 80, false, false>>},
+    // d / e: conv4 on the 64-byte swizzled window at 1 x 4 waves, two patches / one patch per stage
+    {4, 13, row<4, Ws<64, 128, 16, 2, 2, 8, 1, 4, false, 0, 64, false, false>>},
+    {4, 14, row<4, Ws<64, 128, 16, 2, 1, 8, 1, 4, false, 0, 64, false, false>>},
+    // i on conv3: PST, 12.8 vs 12.1 ms for the CST form (same-box A/B; the DEEP producers' two extra barriers
+    // per tile cost more than the MFMA waves' whole-row stores)
+    {3, 18, row<3, Ws<64, 64, 16, 1, 1, 16, 2, 2, false, 0, 80, false, true>>},
+    // 8 / 9 / 4: ablation builds (timing only, wrong results) of k_conv_ws, ABL 45 / 8 / 40
+    {3, 8, row<3, Ws<64, 64, 16, 1, 1, 16, 2, 2, false, 45, 80, false, false>>},
+    {4, 8, row<4, Ws<64, 128, 16, 2, 1, 8, 1, 4, false, 45, 80, false, false>>},
+    {5, 8, row<5, Ws<128, 128, 8, 1, 2, 8, 1, 4, false, 45, 80, false, false>>},
+    {3, 9, row<3, Ws<64, 64, 16, 1, 1, 16, 2, 2, false, 8, 80, false, false>>},
+    {4, 9, row<4, Ws<64, 128, 16, 2, 1, 8, 1, 4, false, 8, 80, false, false>>},
+    {5, 9, row<5, Ws<128, 128, 8, 1, 2, 8, 1, 4, false, 8, 80, false, false>>},
+    {3, 4, row<3, Ws<64, 64, 16, 1, 1, 16, 2, 2, false, 40, 80, false, false>>},
+    {4, 4, row<4, Ws<64, 128, 16, 2, 1, 8, 1, 4, false, 40, 80, false, false>>},
+    {5, 4, row<5, Ws<128, 128, 8, 1, 2, 8, 1, 4, false, 40, 80, false, false>>},
 #endif
+};
+static_assert(hn_rows_unique(kConvRows), "one build per (layer, HN_VARIANT digit)");
 
-// wider N tiles (fewer A-fragment reads, weights shared through L1)
-#ifdef HN_EXPERIMENTS  // superseded tiling (experiments library only)
-HN_WS(ws3_w8, 64, 64, 16, 1, 1, 16, 4, 1)
-HN_WS(ws4_w8, 64, 128, 16, 2, 1, 8, 2, 2)
-HN_WS(ws5_w8, 128, 128, 8, 1, 2, 8, 2, 2)
-#endif
-#ifdef HN_EXPERIMENTS
-// ablation builds (timing only, wrong results; the HN_EXPERIMENTS library only): weights
-// fetched once per stage
-HN_WS_A(ws3_a1, false, 64, 64, 16, 1, 1, 16, 2, 2, 45)
-HN_WS_A(ws4_a1, false, 64, 128, 16, 2, 1, 8, 1, 4, 45)
-HN_WS_A(ws5_a1, false, 128, 128, 8, 1, 2, 8, 1, 4, 45)
-HN_WS_A(ws3_a2, false, 64, 64, 16, 1, 1, 16, 2, 2, 8)
-HN_WS_A(ws4_a2, false, 64, 128, 16, 2, 1, 8, 1, 4, 8)
-HN_WS_A(ws5_a2, false, 128, 128, 8, 1, 2, 8, 1, 4, 8)
-HN_WS_A(ws3_a3, false, 64, 64, 16, 1, 1, 16, 2, 2, 40)
-HN_WS_A(ws4_a3, false, 64, 128, 16, 2, 1, 8, 1, 4, 40)
-HN_WS_A(ws5_a3, false, 128, 128, 8, 1, 2, 8, 1, 4, 40)
-#endif
+}  // namespace
 
 hipError_t hn_launch_stem(const float* in, float* out, const float* w, const float* b, int P,
                           bool norm, float eps, hipStream_t st) {
@@ -1967,142 +1953,16 @@ hipError_t hn_launch_stem(const float* in, float* out, const float* w, const flo
   return hipGetLastError();
 }
 
-// HN_VARIANT digit v is a tiling this library has for conv layer `layer` (0 = stem + conv1,
-// 1 = conv1 alone, 2..5 = conv2..conv5); mirrors the dispatch below.  Digits 4 / 8 / 9 are the
-// timing-only ablation builds of conv3..conv5 (HN_EXPERIMENTS library only).
-bool hn_hardnet_variant_ok(int layer, int v) {
-  // the product library: the defaults (digits 6 0 5 q i l) and one fallback per stage -- 0 (k_conv3x3)
-  // everywhere, 5 / 6 (warp-specialised, smaller / larger tile) for the HN_NO_C12 stem+conv1 and conv2,
-  // 15 (conv4 on the 64-byte swizzled window with the MFMA waves' own stores, digit f), 16 (direct conv3 /
-  // conv5 with epilogue stores through LDS, digit g), 21 / 26 (1-D Winograd F(2,3), weight ring 6 / 8).
-  // The measured-slower tilings (1, 2, 3, 7, 13, 14, 5 / 6 on conv3..conv5), the Winograd kernels 17 (2-D),
-  // 19 / 20 (shallower rings), 32 / 33 (F(4,3) conv3) and the timing-only ablations exist only with
-  // -DHN_EXPERIMENTS.
-  if (layer < 0 || layer > 5) return false;
+// The (layer, HN_VARIANT digit) build of this library, from the kernel files' tables; null: there is none
+const HnConvRow* hn_hardnet_conv_row(int layer, int variant) {
+  if (const HnConvRow* r = hn_find_row(kConvRows, layer, variant)) return r;
 #ifdef HN_EXPERIMENTS
-  if (v == 18 && layer == 3) return true;
-  if (v == 4 || v == 8 || v == 9) return layer >= 3;
-  if (v == 13 || v == 14) return layer == 4;
-  if (v == 17) return layer == 3 || layer == 5;  // Winograd F(2x2,3x3), hn_wino.hip
-  if (v == 7) return layer >= 3;
-  if (v == 1 || v == 2 || v == 3) return true;
-  if (v == 5 || v == 6) return true;
-  if (v == 19 || v == 20) return layer == 3 || layer == 5;  // 1-D Winograd F(2,3), weight ring 3 / 4
-  if (v == 32 || v == 33) return layer == 3;                 // F(4,3) (k_conv_w4), weight ring 6 / 9 (digits w / x)
-  if ((v >= 22 && v <= 25) || v == 29 || v == 30 || v == 31) return layer == 3 || layer == 5;  // its timing-only ablations (ABL 1 / 2 / 4 / 8; t: 16; u: 32, v: 34)
-  if (v == 34 || v == 35) return layer == 3 || layer == 5;  // wave-priority A/B (y: MFMA waves first, z: producers first)
+  if (const HnConvRow* r = hn_wino_conv_row(layer, variant)) return r;
 #endif
-  if (v == 15 || v == 18) return layer == 4;  // 18: outputs stored by the producer waves
-  if (v == 21 || v == 26) return layer == 3 || layer == 5;  // 1-D Winograd F(2,3) (hn_wino1.hip), weight ring 6 / 8
-  if (v == 16) return layer == 3 || layer == 5;
-  if (v == 5 || v == 6) return layer <= 2;  // (layer 1 always runs conv1_launch)
-  if (v == 0) return true;
-  return false;
+  return hn_wino1_conv_row(layer, variant);
 }
 
-// layer 0 = fused stem (input_norm + conv0) + conv1 from the raw patches
-hipError_t hn_launch_hardnet_conv(int layer, int variant, const HardnetDev& d, const float* in,
-                                  float* out, int P, float eps, hipStream_t st) {
-  if (!hn_hardnet_variant_ok(layer, variant)) return hipErrorInvalidValue;
-#ifdef HN_EXPERIMENTS
-  if (variant == 8 || variant == 9 || variant == 4) {  // ablation (timing only)
-    const int a = variant == 8 ? 1 : variant == 9 ? 2 : 3;
-    switch (layer) {
-      case 3: return (a == 1 ? ws3_a1 : a == 2 ? ws3_a2 : ws3_a3)(in, out, d.wpack[3], d.bias[3], P, nullptr, nullptr, 0.f, st);
-      case 4: return (a == 1 ? ws4_a1 : a == 2 ? ws4_a2 : ws4_a3)(in, out, d.wpack[4], d.bias[4], P, nullptr, nullptr, 0.f, st);
-      case 5: return (a == 1 ? ws5_a1 : a == 2 ? ws5_a2 : ws5_a3)(in, out, d.wpack[5], d.bias[5], P, nullptr, nullptr, 0.f, st);
-    }
-    return hipErrorInvalidValue;
-  }
-#endif
-  if (variant == 15 || (variant == 18 && layer == 4)) {  // conv4, 64-byte swizzled window, two patches per stage
-    if (layer != 4) return hipErrorInvalidValue;
-    return (variant == 18 ? ws4_pst : ws4_np2s22)(in, out, d.wpack[4], d.bias[4], P, nullptr, nullptr, 0.f, st);
-  }
-#ifdef HN_EXPERIMENTS
-  if (variant == 18 && layer == 3) return ws3_pst(in, out, d.wpack[3], d.bias[3], P, nullptr, nullptr, 0.f, st);
-#endif
-#ifdef HN_EXPERIMENTS
-  if (variant == 13 || variant == 14) {  // conv4, 64-byte swizzled window (2 / 1 patches per stage)
-    if (layer != 4) return hipErrorInvalidValue;
-    return (variant == 13 ? ws4_np2s : ws4_s)(in, out, d.wpack[4], d.bias[4], P, nullptr, nullptr, 0.f, st);
-  }
-  if (variant == 17) return hn_launch_wino(layer, d, in, out, P, st);
-  if (variant == 7) {  // warp-specialised, NT = 2
-    switch (layer) {
-      case 3: return ws3_w8(in, out, d.wpack[3], d.bias[3], P, nullptr, nullptr, 0.f, st);
-      case 4: return ws4_w8(in, out, d.wpack[4], d.bias[4], P, nullptr, nullptr, 0.f, st);
-      case 5: return ws5_w8(in, out, d.wpack[5], d.bias[5], P, nullptr, nullptr, 0.f, st);
-    }
-    return hipErrorInvalidValue;
-  }
-#endif
-  if (variant == 21) return hn_launch_wino1(layer, 6, d, in, out, P, st);
-  if (variant == 26) return hn_launch_wino1(layer, 8, d, in, out, P, st);
-#ifdef HN_EXPERIMENTS
-  if (variant == 19 || variant == 20) return hn_launch_wino1(layer, variant == 19 ? 3 : 4, d, in, out, P, st);
-  if (variant == 32 || variant == 33) return hn_launch_wino4(layer, variant == 32 ? 6 : 9, d, in, out, P, st);
-  if (variant >= 22 && variant <= 25) return hn_launch_wino1(layer, 100 + (1 << (variant - 22)), d, in, out, P, st);
-  if (variant == 29) return hn_launch_wino1(layer, 116, d, in, out, P, st);
-  if (variant == 30 || variant == 31) return hn_launch_wino1(layer, variant == 30 ? 132 : 134, d, in, out, P, st);
-  if (variant == 34 || variant == 35) return hn_launch_wino1(layer, variant == 34 ? 164 : 228, d, in, out, P, st);
-#endif
-  if (variant == 16) {  // coalesced epilogue stores
-    switch (layer) {
-      case 3: return ws3_cst(in, out, d.wpack[3], d.bias[3], P, nullptr, nullptr, 0.f, st);
-      case 5: return pipe5_cst(in, out, d.wpack[5], d.bias[5], P, nullptr, nullptr, 0.f, st);
-    }
-    return hipErrorInvalidValue;
-  }
-  if (variant == 5 || variant == 6) {  // warp-specialised: 5 = smaller tile, 6 = larger
-    const bool big = variant == 6;
-    switch (layer) {
-      case 0:
-        return (big ? ws1s_t8 : ws1s)(in, out, d.wpack[1], d.bias[1], P, d.stem_w, d.stem_b, eps, st);
-      case 2: return (big ? ws2_t2 : ws2)(in, out, d.wpack[2], d.bias[2], P, nullptr, nullptr, 0.f, st);
-#ifdef HN_EXPERIMENTS
-      case 3: return (big ? ws3_t16 : ws3)(in, out, d.wpack[3], d.bias[3], P, nullptr, nullptr, 0.f, st);
-      case 4: return (big ? ws4_t8 : ws4)(in, out, d.wpack[4], d.bias[4], P, nullptr, nullptr, 0.f, st);
-      case 5: return (big ? ws5_np2 : ws5)(in, out, d.wpack[5], d.bias[5], P, nullptr, nullptr, 0.f, st);
-#endif
-    }
-    return hipErrorInvalidValue;
-  }
-#ifdef HN_EXPERIMENTS
-  if (variant >= 2) {  // persistent pipelined kernels: 2 = smaller tile, 3 = larger tile
-    const bool big = variant == 3;
-    switch (layer) {
-      case 0:
-        return (big ? pipe1s_t8 : pipe1s)(in, out, d.wpack[1], d.bias[1], P, d.stem_w, d.stem_b, eps, st);
-      case 2: return (big ? pipe2 : pipe2_t2)(in, out, d.wpack[2], d.bias[2], P, nullptr, nullptr, 0.f, st);
-      case 3: return (big ? pipe3_t16 : pipe3)(in, out, d.wpack[3], d.bias[3], P, nullptr, nullptr, 0.f, st);
-      case 4: return (big ? pipe4_t8 : pipe4)(in, out, d.wpack[4], d.bias[4], P, nullptr, nullptr, 0.f, st);
-      case 5: return (big ? pipe5_np2 : pipe5)(in, out, d.wpack[5], d.bias[5], P, nullptr, nullptr, 0.f, st);
-    }
-    return hipErrorInvalidValue;
-  }
-#endif
-#ifdef HN_EXPERIMENTS
-  if (variant == 1) {
-    switch (layer) {
-      case 0: return conv1s_v1(in, out, d.wpack[1], d.bias[1], P, d.stem_w, d.stem_b, eps, st);
-      case 2: return conv2_v1(in, out, d.wpack[2], d.bias[2], P, nullptr, nullptr, 0.f, st);
-      case 3: return conv3_v1(in, out, d.wpack[3], d.bias[3], P, nullptr, nullptr, 0.f, st);
-      case 4: return conv4_v1(in, out, d.wpack[4], d.bias[4], P, nullptr, nullptr, 0.f, st);
-      case 5: return conv5_v1(in, out, d.wpack[5], d.bias[5], P, nullptr, nullptr, 0.f, st);
-    }
-  }
-#endif
-  switch (layer) {
-    case 0: return conv1s_launch(in, out, d.wpack[1], d.bias[1], P, d.stem_w, d.stem_b, eps, st);
-    case 1: return conv1_launch(in, out, d.wpack[1], d.bias[1], P, nullptr, nullptr, 0.f, st);
-    case 2: return conv2_launch(in, out, d.wpack[2], d.bias[2], P, nullptr, nullptr, 0.f, st);
-    case 3: return conv3_launch(in, out, d.wpack[3], d.bias[3], P, nullptr, nullptr, 0.f, st);
-    case 4: return conv4_launch(in, out, d.wpack[4], d.bias[4], P, nullptr, nullptr, 0.f, st);
-    case 5: return conv5_launch(in, out, d.wpack[5], d.bias[5], P, nullptr, nullptr, 0.f, st);
-  }
-  return hipErrorInvalidValue;
-}
+bool hn_hardnet_variant_ok(int layer, int variant) { return hn_hardnet_conv_row(layer, variant) != nullptr; }
 
 // Train mode (hn_train.hip): layer `layer`'s production tiling as a plain convolution over NHWC
 // fp32 -- zero bias, no ReLU floor -- with bf16x3 fragments packed on the GPU (k_pack3x3).  The
@@ -2112,11 +1972,11 @@ hipError_t hn_launch_conv_raw(int layer, const void* wp, const float* zero_bias,
   if (P <= 0) return hipSuccess;
   const float lo = -INFINITY;
   switch (layer) {
-    case 1: return conv1_launch_lo(in, out, wp, zero_bias, P, nullptr, nullptr, 0.f, st, lo);
-    case 2: return ws2_lo(in, out, wp, zero_bias, P, nullptr, nullptr, 0.f, st, lo);
-    case 3: return ws3_cst_lo(in, out, wp, zero_bias, P, nullptr, nullptr, 0.f, st, lo);
-    case 4: return ws4_np2s22_lo(in, out, wp, zero_bias, P, nullptr, nullptr, 0.f, st, lo);
-    case 5: return pipe5_cst_lo(in, out, wp, zero_bias, P, nullptr, nullptr, 0.f, st, lo);
+    case 1: return conv_launch<Conv1>(in, out, wp, zero_bias, P, nullptr, nullptr, 0.f, st, lo);
+    case 2: return conv_launch<Ws2>(in, out, wp, zero_bias, P, nullptr, nullptr, 0.f, st, lo);
+    case 3: return conv_launch<Ws3Cst>(in, out, wp, zero_bias, P, nullptr, nullptr, 0.f, st, lo);
+    case 4: return conv_launch<Ws4Np2>(in, out, wp, zero_bias, P, nullptr, nullptr, 0.f, st, lo);
+    case 5: return conv_launch<Pipe5Cst>(in, out, wp, zero_bias, P, nullptr, nullptr, 0.f, st, lo);
   }
   return hipErrorInvalidValue;
 }
@@ -2162,15 +2022,13 @@ hipError_t hn_launch_head(const float* a, float* out, const void* wp, const floa
   }
   if (form >= 4 && P >= 240 * 256) {
 #ifdef HN_EXPERIMENTS  // (ahead of the prefetching form, which has no ablation builds)
-    if (const char* e = std::getenv("HN_HEAD_ABL")) {
-      const int abl = std::atoi(e);
-      if (K == 8192 && !f16 && (abl == 1 || abl == 2 || abl == 3)) {
-        const dim3 g((P + 255) / 256), b(512);
-        if (abl == 1) hipLaunchKernelGGL((k_head4<8192, false, 3, 3, 1>), g, b, 0, st, a, out, w, bias, P, l2eps);
-        if (abl == 2) hipLaunchKernelGGL((k_head4<8192, false, 3, 3, 2>), g, b, 0, st, a, out, w, bias, P, l2eps);
-        if (abl == 3) hipLaunchKernelGGL((k_head4<8192, false, 3, 3, 3>), g, b, 0, st, a, out, w, bias, P, l2eps);
-        return hipGetLastError();
-      }
+    const int abl = hn_knobs().head_abl;
+    if (K == 8192 && !f16 && (abl == 1 || abl == 2 || abl == 3)) {
+      const dim3 g((P + 255) / 256), b(512);
+      if (abl == 1) hipLaunchKernelGGL((k_head4<8192, false, 3, 3, 1>), g, b, 0, st, a, out, w, bias, P, l2eps);
+      if (abl == 2) hipLaunchKernelGGL((k_head4<8192, false, 3, 3, 2>), g, b, 0, st, a, out, w, bias, P, l2eps);
+      if (abl == 3) hipLaunchKernelGGL((k_head4<8192, false, 3, 3, 3>), g, b, 0, st, a, out, w, bias, P, l2eps);
+      return hipGetLastError();
     }
 #endif
     if (hn_knobs().head_pf && K == 8192 && !f16) {
@@ -2199,11 +2057,11 @@ hipError_t hn_launch_head(const float* a, float* out, const void* wp, const floa
 // LDS bytes of each conv config (exported for tests / DESIGN.md)
 int hn_conv_lds_bytes(int layer) {
   switch (layer) {
-    case 1: return conv1_launch_cfg::LDS;
-    case 2: return conv2_launch_cfg::LDS;
-    case 3: return conv3_launch_cfg::LDS;
-    case 4: return conv4_launch_cfg::LDS;
-    case 5: return conv5_launch_cfg::LDS;
+    case 1: return Conv1::Cfg::LDS;
+    case 2: return Conv2::Cfg::LDS;
+    case 3: return Conv3::Cfg::LDS;
+    case 4: return Conv4::Cfg::LDS;
+    case 5: return Conv5::Cfg::LDS;
   }
   return -1;
 }

@@ -2,13 +2,17 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <type_traits>
+
 #include "hardnet_mi355x.h"
 
 // A/B switches of the launchers.  Read from the environment once per model in hn_create (and
 // once per process for the model-less entry points); hn_forward makes the calling model's
 // set current for the duration of the call (thread-local), so launchers never call getenv.
 // Every switch selects a parity-tested alternative kernel; the ablation switches (c12_abl,
-// dbg: timing-only builds with wrong results) exist only in the HN_EXPERIMENTS library.
+// head_abl, w4_abl, pairdist_abl, dbg: timing-only builds with wrong results) exist only in the
+// HN_EXPERIMENTS library.
 struct HnKnobs {
   int c12_cfg = 15;            // HN_C12_CFG: k_c12 configuration (0..15, all within the parity bar; 15 = k_c12s)
   int head = 4;                // HN_HEAD: head GEMM form (1 k_head, 2 k_head2, 3 k_head3 LDS-DMA rings, 4 k_head4 256-patch rings)
@@ -43,6 +47,9 @@ struct HnKnobs {
                                // conv4 k_dgrad2; per wave: conv2 / conv4 k_fwd2)
   int c12w_pd = 11;            // HN_C12W_PD: k_c12w's P2 / P3 B-fragment prefetch distances (tens / units)
   int c12_abl = 0;             // HN_C12_ABL (HN_EXPERIMENTS only)
+  int head_abl = 0;            // HN_HEAD_ABL, HN_W4_ABL, HN_PAIRDIST_ABL (HN_EXPERIMENTS only): timing-only builds of
+  int w4_abl = 0;              // k_head4, k_conv_w4 (HN_VARIANT digit w) and the pair-distance ring
+  int pairdist_abl = 0;
   int dbg = 0;                 // HN_DEBUG (HN_EXPERIMENTS only)
 };
 void hn_read_knobs(HnKnobs* k);
@@ -80,18 +87,101 @@ hipError_t hn_launch_c12(const float* in, float* out, const HardnetDev& d, int P
 
 hipError_t hn_launch_stem(const float* in, float* out, const float* w, const float* b, int P,
                           bool norm, float eps, hipStream_t st);
-bool hn_hardnet_variant_ok(int layer, int variant);
-bool hn_c12_cfg_ok(int cfg, int abl);
-// HN_C12_CFG 14: k_c12w (hn_c12w.hip), conv1 as a 1-D Winograd F(4,3)
-constexpr int kC12Wino = 14;
-// HN_C12_CFG 15: k_c12s (hn_c12w.hip), k_c12w's arithmetic with conv1 / conv2+stem waves per SIMD
-constexpr int kC12Split = 15;
-hipError_t hn_launch_c12s(const float* in, float* out, const HardnetDev& d, int P, float eps, hipStream_t st,
-                          const HnU8In* u8);
-hipError_t hn_launch_c12w(const float* in, float* out, const HardnetDev& d, int P, float eps, hipStream_t st,
-                          const HnU8In* u8, int abl);
-hipError_t hn_launch_hardnet_conv(int layer, int variant, const HardnetDev& d, const float* in,
-                                  float* out, int P, float eps, hipStream_t st);
+// One build of a HardNet conv layer's kernel: `layer` is the HN_VARIANT position (0 = stem + conv1 from the raw
+// patches, 1 = conv1 alone, 2..5 = conv2..conv5), `variant` its digit (0-9, a-z = 10..35).  Each kernel file owns
+// constexpr rows for the kernels it defines (hn_hardnet.hip, hn_wino1.hip; hn_wino.hip in the experiments
+// library) and a static_assert that they are unique; a new kernel build is one more row.  hn_create resolves a
+// model's six rows once: what it accepts is what the forward launches.
+using HnConvLaunch = hipError_t (*)(const HardnetDev& d, const float* in, float* out, int P, float eps,
+                                    hipStream_t st);
+struct HnConvRow {
+  int layer, variant;
+  HnConvLaunch launch;
+};
+template <int N>
+constexpr const HnConvRow* hn_find_row(const HnConvRow (&rows)[N], int layer, int variant) {
+  for (const HnConvRow& r : rows)
+    if (r.layer == layer && r.variant == variant) return &r;
+  return nullptr;
+}
+template <int N>
+constexpr bool hn_rows_unique(const HnConvRow (&rows)[N]) {
+  for (int i = 0; i < N; ++i)
+    if (hn_find_row(rows, rows[i].layer, rows[i].variant) != &rows[i]) return false;
+  return true;
+}
+const HnConvRow* hn_hardnet_conv_row(int layer, int variant);  // across the files; null: no such build here
+const HnConvRow* hn_wino1_conv_row(int layer, int variant);    // hn_wino1.hip's rows
+const HnConvRow* hn_wino_conv_row(int layer, int variant);     // hn_wino.hip's (experiments library only)
+bool hn_hardnet_variant_ok(int layer, int variant);  // hn_hardnet_conv_row found one
+
+// A persistent kernel's launch: grid = min(tiles, resident workgroups) (occupancy query, cached), NTHR threads,
+// SMEM bytes of dynamic LDS
+template <auto Kernel, int NTHR, int SMEM, class... Args>
+hipError_t hn_launch_persistent(int tiles, hipStream_t st, Args... args) {
+  int resident = 0;
+  const hipError_t e = hn_resident_blocks(reinterpret_cast<const void*>(Kernel), NTHR, SMEM, &resident);
+  if (e != hipSuccess) return e;
+  const int grid = std::min(tiles, resident);
+  if (grid <= 0) return hipSuccess;
+  hipLaunchKernelGGL(Kernel, dim3(grid), dim3(NTHR), SMEM, st, args...);
+  return hipGetLastError();
+}
+
+// The builds of the fused stem + conv1 + conv2 kernels, keyed by what selects them: HN_C12_CFG (0..13 k_c12 /
+// k_c12h in hn_c12.hip; 14 = k_c12w, 15 = k_c12s in hn_c12w.hip), HN_C12_ABL and HN_C12W_PD (the last two are
+// 0 / 11 in the product library).  hn_c12_cfg_ok and hn_launch_c12 both read the files' tables.
+using HnC12Launch = hipError_t (*)(const float* in, float* out, const HardnetDev& d, int P, float eps,
+                                   hipStream_t st, const HnU8In* u8);
+constexpr int kAnyPd = -1;  // a row's pd: HN_C12W_PD selects nothing for this (cfg, abl)
+struct HnC12Row {
+  int cfg, abl, pd;
+  HnC12Launch launch;
+};
+constexpr int kC12Wino = 14;   // k_c12w: conv1 as a 1-D Winograd F(4,3)
+constexpr int kC12Split = 15;  // k_c12s: k_c12w's arithmetic with conv1 / conv2+stem waves per SIMD
+template <int N>  // the first matching row: a (cfg, abl)'s exact-pd rows stand before its kAnyPd row
+constexpr const HnC12Row* hn_find_row(const HnC12Row (&rows)[N], int cfg, int abl, int pd) {
+  for (const HnC12Row& r : rows)
+    if (r.cfg == cfg && r.abl == abl && (r.pd == pd || r.pd == kAnyPd)) return &r;
+  return nullptr;
+}
+template <int N>
+constexpr bool hn_rows_unique(const HnC12Row (&rows)[N]) {
+  for (int i = 0; i < N; ++i)
+    if (hn_find_row(rows, rows[i].cfg, rows[i].abl, rows[i].pd) != &rows[i]) return false;
+  return true;
+}
+const HnC12Row* hn_c12_row(int cfg, int abl, int pd);   // across both files; null: no such build here
+const HnC12Row* hn_c12w_row(int cfg, int abl, int pd);  // hn_c12w.hip's rows
+bool hn_c12_cfg_ok(int cfg, int abl, int pd);            // hn_c12_row found one
+// One launch of a fused kernel (the four share their argument list): w1 = conv1's weights in the kernel's layout,
+// grid = min(P, resident workgroups of Base) -- Base is the configuration's fp32, ABL = 0 build
+template <auto Kernel, auto Base, int NTHR>
+hipError_t hn_c12_launch(const void* w1, const float* in, float* out, const HardnetDev& d, int P, float eps,
+                         hipStream_t st, const HnU8In* u8) {
+  int resident = 0;
+  const hipError_t e = hn_resident_blocks(reinterpret_cast<const void*>(Base), NTHR, 0, &resident);
+  if (e != hipSuccess) return e;
+  const int grid = (int)std::min<long>((long)P, resident);
+  const void* src = u8 ? u8->in : static_cast<const void*>(in);
+  hipLaunchKernelGGL(Kernel, dim3(grid), dim3(NTHR), 0, st, src, out, d.stem_w, d.stem_b, static_cast<const uint4*>(w1),
+                     d.bias[1], static_cast<const uint4*>(d.c12_w2), d.bias[2], P, eps, u8 ? u8->mean : 0.f,
+                     u8 ? u8->stdv : 1.f, u8 ? u8->normalize : 0);
+  return hipGetLastError();
+}
+// The fp32 / uint8 choice of the fused kernels' U8 template argument: calls f(std::integral_constant<int, U8>)
+// with U8 = -1 for fp32 input (u8 null), else the uint8 patches' enum hn_resize
+template <class F>
+hipError_t hn_with_u8(const HnU8In* u8, F&& f) {
+  if (!u8) return f(std::integral_constant<int, -1>{});
+  switch (u8->resize) {
+    case HN_RESIZE_NONE: return f(std::integral_constant<int, HN_RESIZE_NONE>{});
+    case HN_RESIZE_CV2_LINEAR: return f(std::integral_constant<int, HN_RESIZE_CV2_LINEAR>{});
+    case HN_RESIZE_PIL_BILINEAR: return f(std::integral_constant<int, HN_RESIZE_PIL_BILINEAR>{});
+  }
+  return hipErrorInvalidValue;
+}
 // part: scratch for the split-K partials of small batches (P <= kHeadSplitMaxP: head_split(K) x P x 128
 // floats), or null for the unsplit forms
 constexpr int kHeadSplitMaxP = 16384;
@@ -103,15 +193,7 @@ int hn_conv_lds_bytes(int layer);
 // in the pack_conv3x3 layout
 hipError_t hn_launch_conv_raw(int layer, const void* wp, const float* zero_bias, const float* in, float* out,
                               int P, hipStream_t st);
-// 1-D Winograd F(2,3) conv3 / conv5 (hn_wino1.hip; HN_VARIANT digit j)
-hipError_t hn_launch_wino1(int layer, int wd, const HardnetDev& d, const float* in, float* out, int P,
-                           hipStream_t st);
 int hn_wino1_lds_bytes(int layer);
-// conv3 as 1-D Winograd F(4,3) (hn_wino1.hip k_conv_w4; HN_VARIANT digits w / x)
-hipError_t hn_launch_wino4(int layer, int wd, const HardnetDev& d, const float* in, float* out, int P,
-                           hipStream_t st);
-// Winograd F(2x2,3x3) conv3 / conv5 (hn_wino.hip; HN_VARIANT digit h)
-hipError_t hn_launch_wino(int layer, const HardnetDev& d, const float* in, float* out, int P, hipStream_t st);
 
 hipError_t hn_launch_pw(const float* in, float* out, const float* wt, const float* bias,
                         const float* res, long npix, int cin, int cout, int groups, bool relu,

@@ -802,8 +802,7 @@ hipError_t hn_launch_pairdist_rows(const float* a, int NA, int row0, const float
     unsigned* cm = reinterpret_cast<unsigned*>(colmin);
     const bool spread = hn_knobs().pairdist_spread;
 #ifdef HN_EXPERIMENTS
-    const char* abl_e = std::getenv("HN_PAIRDIST_ABL");
-    const int abl = abl_e ? std::atoi(abl_e) : 0;
+    const int abl = hn_knobs().pairdist_abl;
     if (ring && colmin && abl > 0) {
       switch (abl) {
         case 1: hipLaunchKernelGGL((k_pairdist_ring<true, NW, 1>), grid, block, 0, st, a, NA, row0, ph, pl, B, asq, psq, xthr, rowmin, cm); break;

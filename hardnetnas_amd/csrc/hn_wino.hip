@@ -346,38 +346,38 @@ __global__ __launch_bounds__(256, 1) void k_wino(const float* __restrict__ in, f
 }
 
 
-template <int CIN, int COUT, int H, int ABL = 0>
-hipError_t launch_wino(const float* in, float* out, const void* wu, const float* bias, int P, hipStream_t st) {
+// A table row's launcher: conv layer L (3: 64 -> 64 at 16x16, 5: 128 -> 128 at 8x8), ablation build ABL
+template <int L, int CIN, int COUT, int H, int ABL>
+hipError_t launch_wino(const HardnetDev& d, const float* in, float* out, int P, hipStream_t st) {
   using C = WinoCfg<CIN, COUT, H>;
-  const void* fn = reinterpret_cast<const void*>(&k_wino<CIN, COUT, H, ABL>);
-  int resident = 0;
-  const hipError_t e = hn_resident_blocks(fn, 256, 0, &resident);  // LDS is static (C::SMEM)
-  if (e != hipSuccess) return e;
-  if (resident < 1) return hipErrorLaunchOutOfResources;
-  const int items = (P + C::NPB - 1) / C::NPB * C::NCB;
-  const int grid = std::min(items, resident);
-  hipLaunchKernelGGL((k_wino<CIN, COUT, H, ABL>), dim3(grid), dim3(256), 0, st, in, out,
-                     static_cast<const uint4*>(wu), bias, P);
-  return hipGetLastError();
+  if (P <= 0) return hipSuccess;
+  if (!d.wino[L]) return hipErrorInvalidValue;
+  // LDS is static (C::SMEM)
+  return hn_launch_persistent<&k_wino<CIN, COUT, H, ABL>, 256, 0>((P + C::NPB - 1) / C::NPB * C::NCB, st, in, out,
+                                                                  static_cast<const uint4*>(d.wino[L]), d.bias[L], P);
 }
+// HN_DEBUG selects the timing-only ablation builds (wrong results)
+template <int L, int CIN, int COUT, int H>
+hipError_t wino_row(const HardnetDev& d, const float* in, float* out, int P, float, hipStream_t st) {
+  switch (hn_knobs().dbg) {
+    case 1: return launch_wino<L, CIN, COUT, H, 1>(d, in, out, P, st);
+    case 2: return launch_wino<L, CIN, COUT, H, 2>(d, in, out, P, st);
+    case 3: return launch_wino<L, CIN, COUT, H, 3>(d, in, out, P, st);
+    case 4: return launch_wino<L, CIN, COUT, H, 4>(d, in, out, P, st);
+    case 8: return launch_wino<L, CIN, COUT, H, 8>(d, in, out, P, st);
+    case 12: return launch_wino<L, CIN, COUT, H, 12>(d, in, out, P, st);
+    case 15: return launch_wino<L, CIN, COUT, H, 15>(d, in, out, P, st);
+  }
+  return launch_wino<L, CIN, COUT, H, 0>(d, in, out, P, st);
+}
+
+// {layer, HN_VARIANT digit, launcher} of this file's builds (hn_internal.h): digit h
+constexpr HnConvRow kWinoRows[] = {
+    {3, 17, wino_row<3, 64, 64, 16>},
+    {5, 17, wino_row<5, 128, 128, 8>},
+};
+static_assert(hn_rows_unique(kWinoRows), "one build per (layer, HN_VARIANT digit)");
 
 }  // namespace
 
-// layer 3 (64 -> 64, 16x16) or 5 (128 -> 128, 8x8)
-hipError_t hn_launch_wino(int layer, const HardnetDev& d, const float* in, float* out, int P, hipStream_t st) {
-  if (P <= 0) return hipSuccess;
-  if (!d.wino[layer]) return hipErrorInvalidValue;
-#ifdef HN_EXPERIMENTS
-#define HN_WABL(A) \
-  if (hn_knobs().dbg == A) \
-    return layer == 3 ? launch_wino<64, 64, 16, A>(in, out, d.wino[3], d.bias[3], P, st) \
-                      : launch_wino<128, 128, 8, A>(in, out, d.wino[5], d.bias[5], P, st);
-  HN_WABL(1) HN_WABL(2) HN_WABL(3) HN_WABL(4) HN_WABL(8) HN_WABL(12) HN_WABL(15)
-#undef HN_WABL
-#endif
-  switch (layer) {
-    case 3: return launch_wino<64, 64, 16>(in, out, d.wino[3], d.bias[3], P, st);
-    case 5: return launch_wino<128, 128, 8>(in, out, d.wino[5], d.bias[5], P, st);
-  }
-  return hipErrorInvalidValue;
-}
+const HnConvRow* hn_wino_conv_row(int layer, int variant) { return hn_find_row(kWinoRows, layer, variant); }

@@ -22,8 +22,6 @@
 // 64 bytes per position, 16-byte chunk q at q ^ (wr & 3): a 32x32x16 operand read (one M tile =
 // 32 / NTX consecutive rows x NTX column pairs) and a producer's 8-lane store group are
 // bank-conflict free (tests/test_lds_banks.py).
-#include <cstdlib>
-
 #include "hn_common.h"
 #include "hn_internal.h"
 
@@ -379,19 +377,13 @@ __global__ __launch_bounds__((WM * WN + 4) * 64) void k_conv_w1(const float* __r
   }
 }
 
-template <int CIN, int COUT, int H, int NP, int WM, int WN, bool CST, int WD, int ABL = 0>
-hipError_t launch_w1(const float* in, float* out, const void* wp, const float* bias, int P, hipStream_t st) {
+// A table row's launcher: conv layer L (3 / 5) at weight ring depth WD, ablation build ABL
+template <int L, int CIN, int COUT, int H, int NP, int WM, int WN, bool CST, int WD, int ABL>
+hipError_t launch_w1(const HardnetDev& d, const float* in, float* out, int P, float, hipStream_t st) {
   using C = W1Cfg<CIN, COUT, H, NP, WM, WN, CST>;
-  const void* fn = reinterpret_cast<const void*>(&k_conv_w1<CIN, COUT, H, NP, WM, WN, CST, WD, ABL>);
-  int resident = 0;
-  const hipError_t e = hn_resident_blocks(fn, C::NTHR, C::SMEM, &resident);
-  if (e != hipSuccess) return e;
-  const int tiles = (P + NP - 1) / NP;
-  const int grid = std::min(tiles, resident);
-  if (grid <= 0) return hipSuccess;
-  hipLaunchKernelGGL((k_conv_w1<CIN, COUT, H, NP, WM, WN, CST, WD, ABL>), dim3(grid), dim3(C::NTHR), C::SMEM, st, in, out,
-                     static_cast<const uint4*>(wp), bias, P);
-  return hipGetLastError();
+  if (!d.wino1[L]) return hipErrorInvalidValue;
+  return hn_launch_persistent<&k_conv_w1<CIN, COUT, H, NP, WM, WN, CST, WD, ABL>, C::NTHR, C::SMEM>(
+      (P + NP - 1) / NP, st, in, out, static_cast<const uint4*>(d.wino1[L]), d.bias[L], P);
 }
 
 #ifdef HN_EXPERIMENTS  // F(4,3) conv3 (k_conv_w4): measured slower than k_conv_w1 (11.2 vs 9.9 ms), experiments library only
@@ -733,19 +725,24 @@ __global__ __launch_bounds__((WN + 4) * 64) void k_conv_w4(const float* __restri
   }
 }
 
-template <int CIN, int COUT, int H, int NP, int WN, int WD, int ABL = 0>
-hipError_t launch_w4(const float* in, float* out, const void* wp, const float* bias, int P, hipStream_t st) {
+template <int L, int CIN, int COUT, int H, int NP, int WN, int WD, int ABL>
+hipError_t launch_w4(const HardnetDev& d, const float* in, float* out, int P, hipStream_t st) {
   using C = W4Cfg<CIN, COUT, H, NP, WN>;
-  const void* fn = reinterpret_cast<const void*>(&k_conv_w4<CIN, COUT, H, NP, WN, WD, ABL>);
-  int resident = 0;
-  const hipError_t e = hn_resident_blocks(fn, C::NTHR, C::SMEM, &resident);
-  if (e != hipSuccess) return e;
-  const int tiles = (P + NP - 1) / NP;
-  const int grid = std::min(tiles, resident);
-  if (grid <= 0) return hipSuccess;
-  hipLaunchKernelGGL((k_conv_w4<CIN, COUT, H, NP, WN, WD, ABL>), dim3(grid), dim3(C::NTHR), C::SMEM, st, in, out,
-                     static_cast<const uint4*>(wp), bias, P);
-  return hipGetLastError();
+  if (!d.wino4[L]) return hipErrorInvalidValue;
+  return hn_launch_persistent<&k_conv_w4<CIN, COUT, H, NP, WN, WD, ABL>, C::NTHR, C::SMEM>(
+      (P + NP - 1) / NP, st, in, out, static_cast<const uint4*>(d.wino4[L]), d.bias[L], P);
+}
+// conv3 at weight ring depth WD; HN_W4_ABL: its timing-only ablation builds (ring 6 whatever the digit)
+template <int WD>
+hipError_t launch_w4c3(const HardnetDev& d, const float* in, float* out, int P, float, hipStream_t st) {
+  switch (hn_knobs().w4_abl) {
+    case 1: return launch_w4<3, 64, 64, 16, 1, 4, 6, 1>(d, in, out, P, st);
+    case 2: return launch_w4<3, 64, 64, 16, 1, 4, 6, 2>(d, in, out, P, st);
+    case 16: return launch_w4<3, 64, 64, 16, 1, 4, 6, 16>(d, in, out, P, st);
+    case 32: return launch_w4<3, 64, 64, 16, 1, 4, 6, 32>(d, in, out, P, st);
+    case 34: return launch_w4<3, 64, 64, 16, 1, 4, 6, 34>(d, in, out, P, st);
+  }
+  return launch_w4<3, 64, 64, 16, 1, 4, WD, 0>(d, in, out, P, st);
 }
 
 using W4Conv3 = W4Cfg<64, 64, 16, 1, 4>;
@@ -754,70 +751,52 @@ using W4Conv3 = W4Cfg<64, 64, 16, 1, 4>;
 using W1Conv3 = W1Cfg<64, 64, 16, 1, 2, 2, true>;
 using W1Conv5 = W1Cfg<128, 128, 8, 2, 1, 4, true>;
 
+// conv3: one patch per work tile, 2 x 2 MFMA waves of 2 M tiles; conv5: two patches, 1 x 4 waves
+template <int WD, int ABL>
+constexpr HnConvLaunch w1c3 = launch_w1<3, 64, 64, 16, 1, 2, 2, true, WD, ABL>;
+template <int WD, int ABL>
+constexpr HnConvLaunch w1c5 = launch_w1<5, 128, 128, 8, 2, 1, 4, true, WD, ABL>;
+
+// {layer, HN_VARIANT digit, launcher} of this file's builds (hn_internal.h)
+constexpr HnConvRow kWino1Rows[] = {
+    {3, 21, w1c3<6, 0>},  // l / q: weight ring 6 / 8
+    {3, 26, w1c3<8, 0>},
+    {5, 21, w1c5<6, 0>},
+    {5, 26, w1c5<8, 0>},
+#ifdef HN_EXPERIMENTS
+    {3, 19, w1c3<3, 0>},  // j / k: weight ring 3 / 4, measured slower than 6 / 8
+    {5, 19, w1c5<3, 0>},
+    {3, 20, w1c3<4, 0>},
+    {5, 20, w1c5<4, 0>},
+    // m n o p t u v: the timing-only ablations ABL 1 2 4 8 16 32 34 at weight ring 8 (wrong results)
+    {3, 22, w1c3<8, 1>},
+    {5, 22, w1c5<8, 1>},
+    {3, 23, w1c3<8, 2>},
+    {5, 23, w1c5<8, 2>},
+    {3, 24, w1c3<8, 4>},
+    {5, 24, w1c5<8, 4>},
+    {3, 25, w1c3<8, 8>},
+    {5, 25, w1c5<8, 8>},
+    {3, 29, w1c3<8, 16>},
+    {5, 29, w1c5<8, 16>},
+    {3, 30, w1c3<8, 32>},
+    {5, 30, w1c5<8, 32>},
+    {3, 31, w1c3<8, 34>},
+    {5, 31, w1c5<8, 34>},
+    {3, 34, w1c3<8, 64>},  // y / z: wave-priority A/B (MFMA waves first / producers first)
+    {5, 34, w1c5<8, 64>},
+    {3, 35, w1c3<8, 128>},
+    {5, 35, w1c5<8, 128>},
+    {3, 32, launch_w4c3<6>},  // w / x: conv3 as F(4,3) (k_conv_w4), weight ring 6 / 9
+    {3, 33, launch_w4c3<9>},
+#endif
+};
+static_assert(hn_rows_unique(kWino1Rows), "one build per (layer, HN_VARIANT digit)");
+
 }  // namespace
 
-// conv3: one patch per work tile, 2 x 2 MFMA waves of 2 M tiles; conv5: two patches, 1 x 4 waves.
-// wd: the weight ring depth (HN_VARIANT digit j = 3, k = 4, l = 6, q = 8)
-hipError_t hn_launch_wino1(int layer, int wd, const HardnetDev& d, const float* in, float* out, int P,
-                           hipStream_t st) {
-  if (P <= 0) return hipSuccess;
-  if (!d.wino1[layer]) return hipErrorInvalidValue;
-#ifdef HN_EXPERIMENTS  // wd = 100 + ABL: the timing-only ablations (weight ring 8)
-#define HN_W1_ABL(CI, CO, HH, NPP, WMM, WNN, L)                                                              \
-  if (wd == 101) return launch_w1<CI, CO, HH, NPP, WMM, WNN, true, 8, 1>(in, out, d.wino1[L], d.bias[L], P, st); \
-  if (wd == 102) return launch_w1<CI, CO, HH, NPP, WMM, WNN, true, 8, 2>(in, out, d.wino1[L], d.bias[L], P, st); \
-  if (wd == 104) return launch_w1<CI, CO, HH, NPP, WMM, WNN, true, 8, 4>(in, out, d.wino1[L], d.bias[L], P, st); \
-  if (wd == 108) return launch_w1<CI, CO, HH, NPP, WMM, WNN, true, 8, 8>(in, out, d.wino1[L], d.bias[L], P, st); \
-  if (wd == 116) return launch_w1<CI, CO, HH, NPP, WMM, WNN, true, 8, 16>(in, out, d.wino1[L], d.bias[L], P, st); \
-  if (wd == 132) return launch_w1<CI, CO, HH, NPP, WMM, WNN, true, 8, 32>(in, out, d.wino1[L], d.bias[L], P, st); \
-  if (wd == 134) return launch_w1<CI, CO, HH, NPP, WMM, WNN, true, 8, 34>(in, out, d.wino1[L], d.bias[L], P, st); \
-  if (wd == 164) return launch_w1<CI, CO, HH, NPP, WMM, WNN, true, 8, 64>(in, out, d.wino1[L], d.bias[L], P, st); \
-  if (wd == 228) return launch_w1<CI, CO, HH, NPP, WMM, WNN, true, 8, 128>(in, out, d.wino1[L], d.bias[L], P, st);
-// weight rings 3 / 4 (digits j / k): measured slower than 6 / 8
-#define HN_W1_SHALLOW(CI, CO, HH, NPP, WMM, WNN, L)                                                          \
-  if (wd == 3) return launch_w1<CI, CO, HH, NPP, WMM, WNN, true, 3>(in, out, d.wino1[L], d.bias[L], P, st); \
-  if (wd == 4) return launch_w1<CI, CO, HH, NPP, WMM, WNN, true, 4>(in, out, d.wino1[L], d.bias[L], P, st);
-#else
-#define HN_W1_ABL(CI, CO, HH, NPP, WMM, WNN, L)
-#define HN_W1_SHALLOW(CI, CO, HH, NPP, WMM, WNN, L)
-#endif
-#define HN_W1(L, CI, CO, HH, NPP, WMM, WNN)                                                                      \
-  if (layer == L) {                                                                                             \
-    HN_W1_SHALLOW(CI, CO, HH, NPP, WMM, WNN, L)                                                                 \
-    if (wd == 6) return launch_w1<CI, CO, HH, NPP, WMM, WNN, true, 6>(in, out, d.wino1[L], d.bias[L], P, st); \
-    if (wd == 8) return launch_w1<CI, CO, HH, NPP, WMM, WNN, true, 8>(in, out, d.wino1[L], d.bias[L], P, st); \
-    HN_W1_ABL(CI, CO, HH, NPP, WMM, WNN, L)                                                                     \
-  }
-  HN_W1(3, 64, 64, 16, 1, 2, 2)
-  HN_W1(5, 128, 128, 8, 2, 1, 4)
-#undef HN_W1
-#undef HN_W1_ABL
-#undef HN_W1_SHALLOW
-  return hipErrorInvalidValue;
-}
+const HnConvRow* hn_wino1_conv_row(int layer, int variant) { return hn_find_row(kWino1Rows, layer, variant); }
 
-#ifdef HN_EXPERIMENTS
-// conv3 as F(4,3) (k_conv_w4); wd: the weight ring depth (HN_VARIANT digit w = 6, x = 9)
-hipError_t hn_launch_wino4(int layer, int wd, const HardnetDev& d, const float* in, float* out, int P,
-                           hipStream_t st) {
-  if (P <= 0) return hipSuccess;
-  if (layer != 3 || !d.wino4[layer]) return hipErrorInvalidValue;
-#ifdef HN_EXPERIMENTS
-  if (const char* e = std::getenv("HN_W4_ABL")) {
-    switch (std::atoi(e)) {
-      case 1: return launch_w4<64, 64, 16, 1, 4, 6, 1>(in, out, d.wino4[3], d.bias[3], P, st);
-      case 2: return launch_w4<64, 64, 16, 1, 4, 6, 2>(in, out, d.wino4[3], d.bias[3], P, st);
-      case 16: return launch_w4<64, 64, 16, 1, 4, 6, 16>(in, out, d.wino4[3], d.bias[3], P, st);
-      case 32: return launch_w4<64, 64, 16, 1, 4, 6, 32>(in, out, d.wino4[3], d.bias[3], P, st);
-      case 34: return launch_w4<64, 64, 16, 1, 4, 6, 34>(in, out, d.wino4[3], d.bias[3], P, st);
-    }
-  }
-#endif
-  if (wd == 6) return launch_w4<64, 64, 16, 1, 4, 6>(in, out, d.wino4[3], d.bias[3], P, st);
-  if (wd == 9) return launch_w4<64, 64, 16, 1, 4, 9>(in, out, d.wino4[3], d.bias[3], P, st);
-  return hipErrorInvalidValue;
-}
-#endif  // HN_EXPERIMENTS
 
 // LDS bytes of the layer's configuration (tests / DESIGN.md)
 int hn_wino1_lds_bytes(int layer) {

@@ -209,6 +209,46 @@ def test_create_rejects_ablation_and_unknown_builds(env, val, monkeypatch):
     assert not h.value
 
 
+# the product library's conv builds, (HN_VARIANT position, tiling), and k_c12 configurations
+PRODUCT_CONV_BUILDS = {(0, 0), (0, 5), (0, 6), (1, 0), (1, 5), (1, 6), (2, 0), (2, 5), (2, 6), (3, 0), (3, 16), (3, 21),
+                       (3, 26), (4, 0), (4, 15), (4, 18), (5, 0), (5, 16), (5, 21), (5, 26)}
+PRODUCT_C12_CFGS = {12, 15}
+
+
+def test_create_accepts_exactly_the_product_builds(monkeypatch):
+    """The set of kernel builds hn_create accepts, through HN_VARIANT (each position of the default 605qil
+    replaced by each digit 0-9a-z) and HN_C12_CFG 0..16: HN_ERR_ARG naming the variable exactly for the builds
+    the product library does not have.  An accepted build goes on to the GPU: HN_ERR_NOMEM ("hipMalloc of
+    parameters failed") without one, a model with one."""
+    m, _, _ = build_module("hardnet")
+    blob = N.state_dict_blob(m.state_dict())
+    lib = N.load_library()
+
+    def accepted(env, val):
+        monkeypatch.setenv(env, val)
+        h = ctypes.c_void_p()
+        rc = lib.hn_create(ctypes.byref(N.hardnet_desc()), blob.ctypes.data, blob.size, ctypes.byref(h))
+        err = lib.hn_last_error()
+        monkeypatch.delenv(env)
+        if rc == 0:
+            assert h.value
+            lib.hn_destroy(h)
+            return True
+        assert not h.value
+        if rc == 3:
+            assert b"hipMalloc of parameters failed" in err, err
+            return True
+        assert rc == 1 and env.encode() in err, (env, val, rc, err)
+        return False
+
+    digits = "0123456789abcdefghijklmnopqrstuvwxyz"
+    got = {(pos, v) for pos in range(6) for v, c in enumerate(digits)
+           if accepted("HN_VARIANT", "605qil"[:pos] + c + "605qil"[pos + 1:])}
+    assert got == PRODUCT_CONV_BUILDS, sorted(got ^ PRODUCT_CONV_BUILDS)
+    got = {cfg for cfg in range(17) if accepted("HN_C12_CFG", str(cfg))}
+    assert got == PRODUCT_C12_CFGS, sorted(got)
+
+
 def test_registered_torch_op_and_fake_kernel():
     """torch.ops.hardnet_mi355x.forward exists (registered at import) and its fake kernel gives
     the [B,128] result shape that torch.compile traces with."""

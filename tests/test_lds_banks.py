@@ -11,7 +11,7 @@ GROUPS = [list(range(0, 4)) + list(range(12, 16)) + list(range(20, 28)),
           list(range(4, 12)) + list(range(16, 20)) + list(range(28, 32))]
 GROUPS += [[l + 32 for l in g] for g in GROUPS]
 
-# (CIN, COUT, HIN, S, NP, TR, WM, WN) -- the HN_CONV instantiations
+# (CIN, COUT, HIN, S, NP, TR, WM, WN) -- the k_conv3x3 builds (hn_hardnet.hip kConvRows)
 CONFIGS = {
     "1": (32, 32, 32, 1, 1, 8, 4, 1),
     "1v1": (32, 32, 32, 1, 1, 4, 4, 1),

@@ -14,9 +14,9 @@ from hardnetnas_amd._native import NativeModel  # noqa: E402
 m, fx, _ = build_module("hardnet")
 x = torch.from_numpy(golden_inputs(fx)).cuda()
 os.environ.pop("HN_VARIANT", None)
-ref = NativeModel.from_module(m, "cuda")(x).cpu().numpy()
+ref = NativeModel.from_module(m, "cuda:0")(x).cpu().numpy()
 print("default vs reference vectors", float(np.abs(ref - fx["y"]).max()))
 for v in sys.argv[1:]:
     os.environ["HN_VARIANT"] = v
-    y = NativeModel.from_module(m, "cuda")(x[:255]).cpu().numpy()
+    y = NativeModel.from_module(m, "cuda:0")(x[:255]).cpu().numpy()
     print(v, "max abs vs default", float(np.abs(y - ref[:255]).max()), "vs reference", float(np.abs(y - fx["y"][:255]).max()))
