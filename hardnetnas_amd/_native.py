@@ -55,7 +55,7 @@ EXPORTED = ["hn_param_count", "hn_create", "hn_workspace_bytes", "hn_forward",
             "hn_nas_train_tensor_count", "hn_nas_train_workspace_bytes", "hn_nas_train_forward",
             "hn_nas_train_backward", "hn_hardnet_loss_train_workspace_bytes", "hn_hardnet_loss_train_forward",
             "hn_hardnet_loss_backward", "hn_fpr95_workspace_bytes",
-            "hn_fpr95", "hn_preprocess", "hn_set_profiling",
+            "hn_fpr95", "hn_match_workspace_bytes", "hn_match_nn2", "hn_preprocess", "hn_set_profiling",
             "hn_stage_times", "hn_destroy", "hn_last_error", "hn_abi_version"]
 
 
@@ -105,6 +105,8 @@ def load_library():
         lib.hn_hardnet_loss_backward.argtypes = [P, P, I64, I32, I32, ctypes.c_float, I32, P, P, P, P, S, P]
         lib.hn_fpr95_workspace_bytes.argtypes = [I64, ctypes.POINTER(S)]
         lib.hn_fpr95.argtypes = [P, P, P, I64, I32, P, P, P, S, P]
+        lib.hn_match_workspace_bytes.argtypes = [I64, I64, ctypes.POINTER(S)]
+        lib.hn_match_nn2.argtypes = [P, I64, P, I64, I32, I32, P, P, P, S, P]
         lib.hn_preprocess.argtypes = [P, I64, I32, I32, I32, ctypes.c_float, ctypes.c_float, P, P]
         lib.hn_set_profiling.argtypes = [P, ctypes.c_int]
         lib.hn_stage_times.argtypes = [P, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p),
@@ -120,7 +122,8 @@ def load_library():
                      "hn_hardnet_train_workspace_bytes", "hn_hardnet_train_forward",
                      "hn_hardnet_train_backward", "hn_nas_train_tensor_count", "hn_nas_train_workspace_bytes",
                      "hn_nas_train_forward", "hn_nas_train_backward", "hn_hardnet_loss_train_workspace_bytes",
-                     "hn_hardnet_loss_train_forward", "hn_hardnet_loss_backward"):
+                     "hn_hardnet_loss_train_forward", "hn_hardnet_loss_backward", "hn_match_workspace_bytes",
+                     "hn_match_nn2"):
             getattr(lib, name).restype = ctypes.c_int
         if lib.hn_abi_version() != ABI_VERSION:
             raise RuntimeError(f"{path}: ABI version {lib.hn_abi_version()}, expected {ABI_VERSION}; rebuild it")
@@ -455,6 +458,49 @@ def fpr95(out_a: torch.Tensor, out_p: torch.Tensor, labels: torch.Tensor):
         _check(lib.hn_fpr95(a.data_ptr(), p.data_ptr(), lab.data_ptr(), n, d, dists.data_ptr(),
                             res.data_ptr(), ws.data_ptr(), ws.numel(), stream), "hn_fpr95")
     return float(res.item()), dists
+
+
+MATCH_METRICS = {"unit": 0, "l2": 1}  # enum hn_metric
+
+
+def match_workspace_bytes(n_query: int, n_db: int) -> int:
+    n = ctypes.c_size_t()
+    _check(load_library().hn_match_workspace_bytes(n_query, n_db, ctypes.byref(n)), "hn_match_workspace_bytes")
+    return n.value
+
+
+def match_nn2(query: torch.Tensor, db: torch.Tensor, metric: str = "unit",
+              workspace: Optional[torch.Tensor] = None):
+    """Nearest and second-nearest row of ``db`` [M,128] for every row of ``query`` [N,128] (fp32 HIP
+    tensors) without the N x M matrix: (dist [N,2] fp32, idx [N,2] int32), dist[:,0] <= dist[:,1]; with
+    M == 1 the second place is (+inf, -1).  metric 'unit' is FDLNet's distance_matrix_vector
+    (math_utils.py:8-19, unit descriptors), 'l2' HardNet's (hardnet/Losses.py:5-13).  Equal keys are
+    ordered by database index (include/hardnet_mi355x.h).  The workspace comes from torch's caching
+    allocator unless one of at least match_workspace_bytes(N, M) bytes is passed."""
+    lib = load_library()
+    if metric not in MATCH_METRICS:
+        raise ValueError(f"metric must be one of {sorted(MATCH_METRICS)}")
+    if query.dim() != 2 or db.dim() != 2 or query.shape[1] != db.shape[1] or query.device != db.device:
+        raise ValueError("expected [N,D] queries and [M,D] database rows on one device")
+    if not query.is_cuda or query.dtype != torch.float32 or db.dtype != torch.float32:
+        raise ValueError("expected fp32 HIP tensors")
+    # the C ABI takes 16-byte aligned rows: a contiguous view at an odd storage offset is copied
+    q, b = (x if x.data_ptr() % 16 == 0 else x.clone() for x in (query.contiguous(), db.contiguous()))
+    n, d = q.shape
+    m = b.shape[0]
+    need = match_workspace_bytes(n, m)
+    if workspace is not None and (workspace.dtype != torch.uint8 or workspace.device != q.device
+                                  or not workspace.is_contiguous()):
+        raise ValueError(f"workspace must be a contiguous uint8 tensor on {q.device}")
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 16), device=q.device, dtype=torch.uint8)
+    dist = torch.empty((n, 2), device=q.device, dtype=torch.float32)
+    idx = torch.empty((n, 2), device=q.device, dtype=torch.int32)
+    stream = torch.cuda.current_stream(q.device).cuda_stream
+    with torch.cuda.device(q.device):
+        _check(lib.hn_match_nn2(q.data_ptr(), n, b.data_ptr(), m, d, MATCH_METRICS[metric], dist.data_ptr(),
+                                idx.data_ptr(), workspace.data_ptr(), workspace.numel(), stream), "hn_match_nn2")
+    return dist, idx
 
 
 RESIZE_MODES = {"none": 0, "cv2": 1, "pil": 2}  # enum hn_resize

@@ -1623,6 +1623,40 @@ extern "C" int hn_pairdist_rows(const float* d_anchor_rows, int64_t n_rows, int6
   return HN_OK;
 }
 
+static const char* match_size_error(int64_t n_query, int64_t n_db) {
+  if (n_query < 1 || n_query > (1 << 22)) return "n_query must be 1 .. 2^22";
+  if (n_db < 1 || n_db > (1 << 22)) return "n_db must be 1 .. 2^22";
+  return nullptr;
+}
+
+extern "C" int hn_match_workspace_bytes(int64_t n_query, int64_t n_db, size_t* bytes_out) {
+  if (!bytes_out) return fail(HN_ERR_ARG, "bytes_out is NULL");
+  if (const char* e = match_size_error(n_query, n_db)) return fail(HN_ERR_ARG, e);
+  *bytes_out = hn_match_ws_bytes((long)n_query, (long)n_db);
+  return HN_OK;
+}
+
+extern "C" int hn_match_nn2(const float* d_query, int64_t n_query, const float* d_db, int64_t n_db, int32_t dim,
+                            int32_t metric, float* d_dist, int32_t* d_idx, void* d_workspace,
+                            size_t workspace_bytes, void* hip_stream) {
+  if (dim != 128) return fail(HN_ERR_ARG, "dim must be 128, got " + std::to_string(dim));
+  if (metric != HN_METRIC_UNIT && metric != HN_METRIC_L2)
+    return fail(HN_ERR_ARG, "unknown metric " + std::to_string(metric) + " (HN_METRIC_UNIT, HN_METRIC_L2)");
+  if (const char* e = match_size_error(n_query, n_db)) return fail(HN_ERR_ARG, e);
+  const size_t need = hn_match_ws_bytes((long)n_query, (long)n_db);
+  if (workspace_bytes < need)
+    return fail(HN_ERR_WORKSPACE, "workspace too small: need " + std::to_string(need) + " bytes");
+  if (!d_query || !d_db || !d_dist || !d_idx || !d_workspace) return fail(HN_ERR_ARG, "NULL device pointer");
+  if ((reinterpret_cast<uintptr_t>(d_query) | reinterpret_cast<uintptr_t>(d_db) |
+       reinterpret_cast<uintptr_t>(d_workspace)) & 15)
+    return fail(HN_ERR_ARG, "d_query / d_db / d_workspace must be 16-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(d_dist) | reinterpret_cast<uintptr_t>(d_idx)) & 7)
+    return fail(HN_ERR_ARG, "d_dist / d_idx must be 8-byte aligned");
+  HIPCHK(hn_launch_match_nn2(d_query, (int)n_query, d_db, (int)n_db, metric, d_dist, d_idx, d_workspace,
+                             static_cast<hipStream_t>(hip_stream)));
+  return HN_OK;
+}
+
 extern "C" int hn_hardnet_loss(const float* d_pos, const float* d_row_min, const float* d_col_min,
                                int64_t n, float margin, int32_t loss_type, float scale,
                                float* d_min_neg, float* d_loss, void* hip_stream) {

@@ -217,6 +217,11 @@ hipError_t hn_launch_pairdist(const float* a, const float* p, int B, int D, int 
 size_t hn_pairdist_rows_ws_bytes(long NA, long B);
 hipError_t hn_launch_pairdist_rows(const float* a, int NA, int row0, const float* p, int B, float* pos,
                                    float* rowmin, float* colmin, void* ws, hipStream_t st);
+hipError_t hn_launch_split_planes(const float* p, int B, uint16_t* ph, uint16_t* pl, hipStream_t st);
+// nearest / second-nearest database row of every query (hn_match.hip): idx [N,2] (-1: no such row), dist [N,2]
+size_t hn_match_ws_bytes(long N, long M);
+hipError_t hn_launch_match_nn2(const float* q, int N, const float* db, int M, int metric, float* dist, int* idx,
+                               void* ws, hipStream_t st);
 hipError_t hn_launch_loss(const float* pos, const float* rmin, const float* cmin, int n, float margin,
                           int type, float scale, float* min_neg, float* loss, hipStream_t st);
 

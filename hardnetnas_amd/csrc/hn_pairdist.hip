@@ -774,6 +774,12 @@ float mask_threshold_x() {
 
 }  // namespace
 
+// bf16 hi / lo planes [B][128] of B fp32 rows (the ring kernels' pre-split operand; hn_match.hip shares it)
+hipError_t hn_launch_split_planes(const float* p, int B, uint16_t* ph, uint16_t* pl, hipStream_t st) {
+  hipLaunchKernelGGL(k_split_planes, dim3((unsigned)(((long)B * 16 + 255) / 256)), dim3(256), 0, st, p, B, ph, pl);
+  return hipGetLastError();
+}
+
 // workspace: |a|^2 [NA] | |p|^2 [B] | (ring form) bf16 hi / lo planes of the positives [B][128] each
 size_t hn_pairdist_rows_ws_bytes(long NA, long B) {
   return (size_t)((NA + 63) / 64 * 64 + (B + 63) / 64 * 64) * sizeof(float) + (size_t)B * 128 * 2 * sizeof(uint16_t);

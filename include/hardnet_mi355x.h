@@ -181,6 +181,33 @@ int hn_fpr95(const float* d_anchor, const float* d_positive, const int32_t* d_la
              int32_t dim, float* d_dists, double* d_fpr, void* d_workspace, size_t workspace_bytes,
              void* hip_stream);
 
+/* Nearest and second-nearest database descriptor of every query, the matching step of FDLNet's evaluation
+ * (FDLNet-master/latency/NASNet/utils/eval_utils.py:112-197 over math_utils.py:8-19), without materialising
+ * the n_query x n_db distance matrix.
+ *   HN_METRIC_UNIT  d(a,b) = sqrt(clamp(2 - 2 a.b, 1e-8, 4))           FDLNet's distance_matrix_vector (unit rows)
+ *   HN_METRIC_L2    d(a,b) = sqrt(|a|^2 + |b|^2 - 2 a.b + 1e-6) + 1e-8  hardnet/Losses.py:5-13
+ * d_query [n_query,128], d_db [n_db,128] fp32 (16-byte aligned).  Outputs (8-byte aligned): d_dist [n_query,2]
+ * fp32 and d_idx [n_query,2] int32, column 0 the nearest database row and column 1 the second-nearest, with
+ * d_dist[i][0] <= d_dist[i][1] and d_idx[i][0] != d_idx[i][1].  With n_db == 1 the second place is
+ * dist = +inf, idx = -1.  1 <= n_query, n_db <= 2^22.
+ * Precision: the two rows are SELECTED on the key c_j - 2 a_i.b_j (c_j = 0 / |b_j|^2: both distances are
+ * monotone in it) with the dot product on the bf16 MFMA in bf16x3 split precision, about 5e-6 absolute on
+ * unit descriptors: a selected row's key exceeds the true minimum (second minimum) by at most twice that
+ * error.  The reported distances are then recomputed for the two selected rows in plain fp32; should they
+ * come out in the other order (keys within the selection error), the pair is swapped.
+ * Ties: rows are ordered lexicographically on (key, index): of equal keys the smaller database index comes
+ * first, for both places, whatever the order the GPU finishes its work in; the call is deterministic and a
+ * query's result does not depend on which other queries share the call.
+ * One deliberate difference from the reference: where several database rows fall inside the clamp
+ * (2 - 2 a.b < 1e-8) the reference's min sees equal distances and returns whichever index torch picks; this
+ * call orders such rows by the unclamped key.
+ * No allocation or synchronisation inside; every argument check runs before the GPU is touched. */
+enum hn_metric { HN_METRIC_UNIT = 0, HN_METRIC_L2 = 1 };
+int hn_match_workspace_bytes(int64_t n_query, int64_t n_db, size_t* bytes_out);
+int hn_match_nn2(const float* d_query, int64_t n_query, const float* d_db, int64_t n_db, int32_t dim,
+                 int32_t metric, float* d_dist, int32_t* d_idx, void* d_workspace, size_t workspace_bytes,
+                 void* hip_stream);
+
 /* Patch preprocessing: uint8 patches -> fp32 [n,1,32,32] network input,
  * bit-exact with the reference loaders.
  *   HN_RESIZE_CV2_LINEAR   hardnet/HardNet.py:345-349 'transform' + Utils.py:10-11 cv2_scale:
