@@ -1047,12 +1047,6 @@ __global__ __launch_bounds__((WM * WN + 4) * 64) void k_conv_ws(
   constexpr unsigned CHUNK_BYTES = 9 * 2 * C::NTOT * 2 * 64 * 16;
   const __amdgpu_buffer_rsrc_t wr_ = make_rsrc(wp, C::NCC * CHUNK_BYTES);
   const unsigned wvoff = (wn * C::NT * 2 * 64 + lane) * 16;
-  f32x16 acc[C::MT][C::NT];
-#pragma unroll
-  for (int mt = 0; mt < C::MT; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < C::NT; ++nt) acc[mt][nt] = f32x16{};
-
   constexpr int NKS = 18;
   // weight fragments of K-step k of channel chunk cc; a stage's first two K-steps are
   // fetched during the previous stage's last two, i.e. before its epilogue stores, which
@@ -1071,10 +1065,15 @@ __global__ __launch_bounds__((WM * WN + 4) * 64) void k_conv_ws(
   uint4 bq[WD][C::NT][2];
 #pragma unroll
   for (int k = 0; k + 1 < WD; ++k) load_b(0, k, bq[k]);
-#pragma unroll 1
-  for (int s = 0; s < NS; ++s) {
+  // A loop over the workgroup's tiles with a tile's NCC stages inside: the accumulators live for one tile
+  // (its first MFMAs take a zero C operand: nothing is zero-filled, selected or carried round the stage
+  // loop) and the epilogue is straight-line code after the tile's last stage.  The producers keep their
+  // flat stage sequence; the barriers pair up one for one.
+  f32x16 acc[C::MT][C::NT];
+  // stage s of the workgroup: channel chunk cc of its tile (ccn: the next stage's chunk); FIRST: cc == 0
+  auto stage = [&](auto first, int s, int cc, int ccn) {
+    constexpr bool FIRST = decltype(first)::value;
     const char* cur = (s & 1) ? buf1 : buf0;
-    const int cc = s % C::NCC, ccn = (s + 1) % C::NCC;
     uint4 aq[2][C::MT][2];
     auto load_a = [&](int ksx, uint4 (&dst)[C::MT][2]) {
       const int tap = (ABL & 2) ? 0 : ksx >> 1, ks = (ABL & 2) ? 0 : ksx & 1;  // ABL 2: timing only
@@ -1100,26 +1099,39 @@ __global__ __launch_bounds__((WM * WN + 4) * 64) void k_conv_ws(
       if constexpr (PST) {
         // B_y of the previous tile (see pstore), at the first K-step: same-box conv4 6.93 ms there,
         // 6.95 at K-step 1, 7.02 at 2, 7.09 at 4; the producers' window writes wait for it
-        if (ksx == 0 && cc == 0 && s > 0) __builtin_amdgcn_s_barrier();
+        if (FIRST && ksx == 0 && s > 0) __builtin_amdgcn_s_barrier();
       }
 #pragma unroll
       for (int mt = 0; mt < C::MT; ++mt) {
         const bf16x8 xh = as_bf16x8(aq[ksx & 1][mt][0]), xl = as_bf16x8(aq[ksx & 1][mt][1]);
 #pragma unroll
         for (int nt = 0; nt < C::NT; ++nt) {
-          if constexpr (ABL & 16)  // timing only: no MFMA, operands kept live
+          // a tile's first MFMAs start its accumulators from a zero C operand
+          const f32x16 c = FIRST && ksx == 0 ? f32x16{} : acc[mt][nt];
+          if constexpr (ABL & 16) {  // timing only: no MFMA, operands kept live
+            acc[mt][nt] = c;
             acc[mt][nt][0] += __builtin_bit_cast(float, aq[ksx & 1][mt][0].x ^ aq[ksx & 1][mt][1].y ^
                                                            bq[ksx % WD][nt][0].z ^ bq[ksx % WD][nt][1].w);
-          else
-            acc[mt][nt] = mfma3(as_bf16x8(bq[ksx % WD][nt][0]), as_bf16x8(bq[ksx % WD][nt][1]), xh,
-                                xl, acc[mt][nt]);
+          } else {
+            acc[mt][nt] = mfma3(as_bf16x8(bq[ksx % WD][nt][0]), as_bf16x8(bq[ksx % WD][nt][1]), xh, xl, c);
+          }
         }
       }
       __builtin_amdgcn_sched_barrier(0);
     }
-    if (PST && cc == C::NCC - 1) {
+  };
+#pragma unroll 1
+  for (int t = 0; t < my_tiles; ++t) {
+    const int s0 = t * C::NCC, s = s0 + C::NCC - 1;  // the tile's first and last stage
+    stage(std::true_type{}, s0, 0, C::NCC > 1 ? 1 : 0);
+#pragma unroll 1
+    for (int cc = 1; cc < C::NCC; ++cc) {
+      if constexpr (!(ABL & 32)) __syncthreads();
+      stage(std::false_type{}, s0 + cc, cc, (cc + 1) % C::NCC);
+    }
+    if constexpr (PST) {
       __syncthreads();  // B_s: the stage's buffer is free
-      char* stg = const_cast<char*>(cur);
+      char* stg = (s & 1) ? buf1 : buf0;
 #pragma unroll
       for (int nt = 0; nt < C::NT; ++nt) {
         float4 bv[4];
@@ -1138,13 +1150,10 @@ __global__ __launch_bounds__((WM * WN + 4) * 64) void k_conv_ws(
             v.w = fmaxf(acc[mt][nt][4 * q + 3] + bv[q].w, relu_lo);
             *reinterpret_cast<float4*>(o + 32 * q) = v;
           }
-          acc[mt][nt] = f32x16{};
         }
       }
       __syncthreads();  // B_x
-      continue;
-    }
-    if (cc == C::NCC - 1) {
+    } else {
       int p0, y0;
       tile_of(s, p0, y0);
       float* obase = out + ((size_t)(p0 * C::HOUT + y0) * C::WOUT + wm * C::MT * 32 + r) * COUT +
@@ -1189,11 +1198,10 @@ __global__ __launch_bounds__((WM * WN + 4) * 64) void k_conv_ws(
             __builtin_amdgcn_wave_barrier();
             asm volatile("" ::: "memory");
           }
-          acc[mt][nt] = f32x16{};
         }
       }
+      if constexpr (!(ABL & 32)) __syncthreads();
     }
-    if constexpr (!(ABL & 32)) __syncthreads();
   }
   if constexpr (PST) __builtin_amdgcn_s_barrier();  // B_y of the last tile
 }

@@ -62,6 +62,29 @@ struct W1Cfg {
   static_assert(RS % 256 == 0, "image rows on 256-byte boundaries (the bank-conflict argument)");
 };
 
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): a loop whose index is a constant expression
+// (sched_group_barrier takes immediates)
+template <int... I, class F>
+HN_DEV void static_for_seq(std::integer_sequence<int, I...>, F&& f) {
+  (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, class F>
+HN_DEV void static_for(F&& f) {
+  static_for_seq(std::make_integer_sequence<int, N>{}, f);
+}
+
+// k_conv_w1's fold schedule (see the kernel): a fold of 16 accumulator entries spread over three MFMA gaps takes
+// entries [w1_lo3(g), w1_lo3(g + 1)) in gap g, one spread over six takes [3 g, 3 g + 3)
+constexpr int w1_lo3(int g) { return g == 0 ? 0 : g == 1 ? 6 : g == 2 ? 11 : 16; }
+// VALU instructions folded into the gap after MFMA g of K-step kx (first: the work tile's first stage)
+constexpr int w1_fold_valu(bool first, int kx, int g) {
+  if (kx == 11 && g >= 3) return 2 * (w1_lo3(g - 2) - w1_lo3(g - 3));
+  if (kx == 12 && g < 3) return 2 * (w1_lo3(g + 1) - w1_lo3(g));
+  if (kx == 18 || kx == 19 || (kx == 0 && !first)) return g < 5 ? 3 : 1;
+  if (kx == 23 && g >= 3) return w1_lo3(g - 2) - w1_lo3(g - 3);
+  return 0;
+}
+
 // ABL (timing-only ablation builds, HN_EXPERIMENTS library only; wrong results): bit 0 idle producers
 // (barriers only), bit 1 no MFMAs (operands still loaded), bit 2 no weight loads (K-step 0's fragments
 // reused), bit 3 no epilogue stores, bit 4 idle MFMA waves, bit 5 no weight loads after the prologue
@@ -241,11 +264,9 @@ __global__ __launch_bounds__((WM * WN + 4) * 64) void k_conv_w1(const float* __r
   }
   const __amdgpu_buffer_rsrc_t wr_ = make_rsrc(wp, C::NCC * C::CHUNK_BYTES);
   const unsigned wvoff = (wn * C::NT * 2 * 64 + lane) * 16;
-  f32x16 y0a[C::MT][C::NT], y1a[C::MT][C::NT], ma[C::MT][C::NT];
-#pragma unroll
-  for (int mt = 0; mt < C::MT; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < C::NT; ++nt) y0a[mt][nt] = y1a[mt][nt] = ma[mt][nt] = f32x16{};
+  // accumulators of the wave's two (mt, nt) tiles: they live for one work tile (the tile loop below)
+  static_assert(C::MT * C::NT == 2, "the fold schedule below is written for two accumulator tiles per wave");
+  f32x16 y0a[2], y1a[2], ma[2];
 
   auto load_b = [&](int cc, int kx, uint4 (&dst)[C::NT][2]) {
 #pragma unroll
@@ -261,10 +282,58 @@ __global__ __launch_bounds__((WM * WN + 4) * 64) void k_conv_w1(const float* __r
   uint4 bq[WD][C::NT][2];
 #pragma unroll
   for (int k = 0; k + 1 < WD; ++k) load_b(0, k, bq[k]);
-#pragma unroll 1
-  for (int s = 0; s < NS; ++s) {
+
+  // The A^T folds of m1 / m2 (in ma) into y0a / y1a run as scalar fp32 adds in the issue gaps behind other
+  // tiles' MFMAs (a packed f32 add beside MFMAs costs several issue slots; an add that waits for the chain that
+  // produced its operand leaves the matrix pipe empty: this wave is the only one feeding it).  Per accumulator
+  // the operations and their order are  y0: xi = 0 chain, + m1, + m2;  y1: + m1, xi = 3 chain, - m2.
+  // Slot g of K-step kx is the gap after the K-step's g-th MFMA (MFMAs 0-2 are tile 0's, 3-5 tile 1's):
+  //   kx 11, g 3-5 (tile 1's last xi = 1 MFMAs)      tile 0: y0 += m1, y1 += m1
+  //   kx 12, g 0-2 (tile 0's first xi = 2 MFMAs)     tile 1: the same, before its MFMA 3 restarts ma
+  //   kx 18 / 19, g 0-5 (y0a idle)                   tile 0 / 1: y0 += m2
+  //   kx 23, g 3-5 (tile 1's last xi = 3 MFMAs)      tile 0: y1 -= m2
+  //   next stage's kx 0, g 0-5 (ma rewritten at 6)   tile 1: y1 -= m2 (after a tile's last stage: exposed,
+  //                                                  once per tile, ahead of the epilogue)
+  // The empty asm keeps each sum a scalar (no re-packing into v_pk_add_f32).
+  auto sadd = [](float a, float b) {
+    float v = a + b;
+    asm("" : "+v"(v));
+    return v;
+  };
+  auto ssub = [](float a, float b) {
+    float v = a - b;
+    asm("" : "+v"(v));
+    return v;
+  };
+  // (w1_fold_valu: the number of VALU instructions fold emits in a slot)
+  auto fold = [&](auto first_, auto kx_, auto g_) {
+    constexpr bool first = decltype(first_)::value;
+    constexpr int kx = decltype(kx_)::value, g = decltype(g_)::value;
+    if constexpr ((kx == 11 && g >= 3) || (kx == 12 && g < 3)) {
+      constexpr int j = kx == 11 ? 0 : 1, g3 = kx == 11 ? g - 3 : g;
+#pragma unroll
+      for (int i = w1_lo3(g3); i < w1_lo3(g3 + 1); ++i) {
+        y0a[j][i] = sadd(y0a[j][i], ma[j][i]);
+        y1a[j][i] = sadd(first ? 0.f : y1a[j][i], ma[j][i]);  // a tile's first stage: y1 starts from zero
+      }
+    } else if constexpr (kx == 18 || kx == 19) {
+#pragma unroll
+      for (int i = 3 * g; i < 3 * g + 3 && i < 16; ++i) y0a[kx - 18][i] = sadd(y0a[kx - 18][i], ma[kx - 18][i]);
+    } else if constexpr (kx == 23 && g >= 3) {
+#pragma unroll
+      for (int i = w1_lo3(g - 3); i < w1_lo3(g - 2); ++i) y1a[0][i] = ssub(y1a[0][i], ma[0][i]);
+    } else if constexpr (kx == 0 && !first) {
+#pragma unroll
+      for (int i = 3 * g; i < 3 * g + 3 && i < 16; ++i) y1a[1][i] = ssub(y1a[1][i], ma[1][i]);
+    }
+  };
+
+  // Stage s of the workgroup: channel chunk cc of its work tile (ccn: the next stage's chunk); FIRST: cc == 0,
+  // the accumulators start from a zero C operand / a zero addend (nothing is zero-filled or carried round
+  // the stage loop).  The producers keep their flat stage sequence; the barriers pair up one for one.
+  auto stage = [&](auto first_, int s, int cc, int ccn) {
+    constexpr bool FIRST = decltype(first_)::value;
     const char* cur = (s & 1) ? buf1 : buf0;
-    const int cc = s % C::NCC, ccn = (s + 1) % C::NCC;
     uint4 aq[2][C::MT][2];
     auto load_a = [&](int kx, uint4 (&dst)[C::MT][2]) {
       const int xi = kx / 6, ky = (kx % 6) >> 1, ks = kx & 1;
@@ -276,55 +345,65 @@ __global__ __launch_bounds__((WM * WN + 4) * 64) void k_conv_w1(const float* __r
       }
     };
     load_a(0, aq[0]);
-#pragma unroll
-    for (int kx = 0; kx < C::NKS; ++kx) {
+    static_for<C::NKS>([&](auto kx_) {
+      constexpr int kx = decltype(kx_)::value, xi = kx / 6;
       if constexpr ((ABL & 32) != 0) {  // timing only: no weight loads after the prologue
-      } else if (kx + WD - 1 < C::NKS)
+      } else if constexpr (kx + WD - 1 < C::NKS)
         load_b(cc, kx + WD - 1, bq[(kx + WD - 1) % WD]);
       else  // the next stage's first fragments, unconditionally (valid weights even after the last
             // stage): a branch here made the compiler's vmcnt merge wait vmcnt(0) at the stage's end
         load_b(ccn, kx + WD - 1 - C::NKS, bq[(kx + WD - 1) % WD]);
-      if (kx + 1 < C::NKS) load_a(kx + 1, aq[(kx + 1) & 1]);
+      if constexpr (kx + 1 < C::NKS) load_a(kx + 1, aq[(kx + 1) & 1]);
       __builtin_amdgcn_sched_barrier(0);
-      const int xi = kx / 6;
-      if (kx == 12) {  // m1 complete: out[2t] += m1, out[2t+1] += m1
-#pragma unroll
-        for (int mt = 0; mt < C::MT; ++mt)
-#pragma unroll
-          for (int nt = 0; nt < C::NT; ++nt) {
-            y0a[mt][nt] += ma[mt][nt];
-            y1a[mt][nt] += ma[mt][nt];
+      // the K-step's six MFMAs (tile j = (mt, nt): bf16x3 products lo x hi, hi x lo, hi x hi as in mfma3), each
+      // followed by its slot of the fold schedule; the group barriers pin the folds into their gaps
+      static_for<6>([&](auto g_) {
+        constexpr int g = decltype(g_)::value, j = g / 3, p = g % 3, mt = j / C::NT, nt = j % C::NT;
+        const bf16x8 x = as_bf16x8(aq[kx & 1][mt][p == 1 ? 1 : 0]), w = as_bf16x8(bq[kx % WD][nt][p == 0 ? 1 : 0]);
+        f32x16& acc = xi == 0 ? y0a[j] : xi == 3 ? y1a[j] : ma[j];
+        // from a zero C operand: m1 (kx 6) / m2 (kx 12), and y0 in a work tile's first stage
+        constexpr bool zero = p == 0 && (kx == 6 || kx == 12 || (kx == 0 && FIRST));
+        if constexpr ((ABL & 2) != 0) {  // timing only: no MFMA, operands kept live
+          if (FIRST && kx == 0 && p == 0) y0a[j] = y1a[j] = ma[j] = f32x16{};
+          if (p == 0)
+            y0a[j][0] += __builtin_bit_cast(float, aq[kx & 1][mt][0].x ^ aq[kx & 1][mt][1].y ^
+                                                       bq[kx % WD][nt][0].z ^ bq[kx % WD][nt][1].w);
+        } else {
+          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w, x, zero ? f32x16{} : acc, 0, 0, 0);
+          constexpr int nv = w1_fold_valu(FIRST, kx, g);
+          if constexpr (nv > 0) {
+            fold(first_, kx_, g_);
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // the MFMA,
+            __builtin_amdgcn_sched_group_barrier(0x002, nv, 0);  // then this slot's adds
+          } else if constexpr (w1_fold_valu(FIRST, kx, 0) + w1_fold_valu(FIRST, kx, 5) > 0) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // (a K-step with folds in its other slots)
           }
-      }
-#pragma unroll
-      for (int mt = 0; mt < C::MT; ++mt) {
-        const bf16x8 xh = as_bf16x8(aq[kx & 1][mt][0]), xl = as_bf16x8(aq[kx & 1][mt][1]);
-#pragma unroll
-        for (int nt = 0; nt < C::NT; ++nt) {
-          const bf16x8 wh = as_bf16x8(bq[kx % WD][nt][0]), wl = as_bf16x8(bq[kx % WD][nt][1]);
-          if constexpr ((ABL & 2) != 0)  // timing only: no MFMA, operands kept live
-            y0a[mt][nt][0] += __builtin_bit_cast(float, aq[kx & 1][mt][0].x ^ aq[kx & 1][mt][1].y ^
-                                                            bq[kx % WD][nt][0].z ^ bq[kx % WD][nt][1].w);
-          else if (xi == 0)
-            y0a[mt][nt] = mfma3(wh, wl, xh, xl, y0a[mt][nt]);
-          else if (xi == 3)
-            y1a[mt][nt] = mfma3(wh, wl, xh, xl, y1a[mt][nt]);
-          else  // m1 (kx 6..11) / m2 (kx 12..17) start from zero
-            ma[mt][nt] = mfma3(wh, wl, xh, xl, (kx % 6 == 0) ? f32x16{} : ma[mt][nt]);
         }
-      }
+      });
       __builtin_amdgcn_sched_barrier(0);
+    });
+  };
+  auto fold_last = [&] {  // tile 1's y1 -= m2 of a work tile's last stage
+#pragma unroll
+    for (int i = 0; i < 16; ++i) y1a[1][i] = ssub(y1a[1][i], ma[1][i]);
+  };
+#pragma unroll 1
+  for (int t = 0; t < my_tiles; ++t) {
+    const int s0 = t * C::NCC, s = s0 + C::NCC - 1;  // the work tile's first and last stage
+    stage(std::true_type{}, s0, 0, C::NCC > 1 ? 1 : 0);
+#pragma unroll 1
+    for (int cc = 1; cc < C::NCC; ++cc) {
+      __syncthreads();
+      stage(std::false_type{}, s0 + cc, cc, (cc + 1) % C::NCC);
     }
-    // m2 complete: out[2t] += m2, out[2t+1] -= m2
-#pragma unroll
-    for (int mt = 0; mt < C::MT; ++mt)
-#pragma unroll
-      for (int nt = 0; nt < C::NT; ++nt) {
-        y0a[mt][nt] += ma[mt][nt];
-        y1a[mt][nt] -= ma[mt][nt];
-      }
-    if (cc == C::NCC - 1) {
+    if constexpr ((ABL & 2) == 0) fold_last();
+    {
       const int p0 = tile_of(s);
+      // the epilogue re-derives its per-lane address terms from an opaque lane id once per work tile: kept in
+      // registers across the stages they push the K-loop over the register budget
+      int le = lane;
+      asm volatile("" : "+v"(le));
+      const int r = le & 31, h = le >> 5;
 #pragma unroll
       for (int nt = 0; nt < C::NT; ++nt) {
         float4 bv[4];
@@ -335,12 +414,12 @@ __global__ __launch_bounds__((WM * WN + 4) * 64) void k_conv_w1(const float* __r
         for (int mt = 0; mt < C::MT; ++mt) {
           const int m0 = (wm * C::MT + mt) * 32;  // the M tile: 32 / NTX whole rows of patch np
           const int np = m0 / (TR * C::NTX), yb = (m0 % (TR * C::NTX)) / C::NTX;
-          if ((NP == 1 || p0 + np < P) && ((ABL & 8) == 0 || y0a[mt][nt][0] == 1234.5f)) {  // ABL 8: timing only
+          if ((NP == 1 || p0 + np < P) && ((ABL & 8) == 0 || y0a[mt * C::NT + nt][0] == 1234.5f)) {  // ABL 8: timing only
             // pixel (row yb + m / NTX, column 2 (m % NTX) + par) of M index m = m0 + m
             float* const ob = out + (((size_t)p0 + np) * H + yb) * H * COUT + (wn * C::NT + nt) * 32;
 #pragma unroll
             for (int par = 0; par < 2; ++par) {
-              const f32x16& yv = par ? y1a[mt][nt] : y0a[mt][nt];
+              const f32x16& yv = par ? y1a[mt * C::NT + nt] : y0a[mt * C::NT + nt];
               float4 v[4];
 #pragma unroll
               for (int q = 0; q < 4; ++q)
@@ -354,7 +433,7 @@ __global__ __launch_bounds__((WM * WN + 4) * 64) void k_conv_w1(const float* __r
                 asm volatile("" ::: "memory");
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                  const int ml = 8 * k + (lane >> 3), c4 = lane & 7;
+                  const int ml = 8 * k + (le >> 3), c4 = le & 7;
                   const int px = (ml / C::NTX) * H + 2 * (ml % C::NTX) + par;
                   *reinterpret_cast<float4*>(ob + (size_t)px * COUT + 4 * c4) =
                       *reinterpret_cast<const float4*>(scr + ml * C::SROW + 4 * c4);
@@ -369,7 +448,6 @@ __global__ __launch_bounds__((WM * WN + 4) * 64) void k_conv_w1(const float* __r
               }
             }
           }
-          y0a[mt][nt] = y1a[mt][nt] = f32x16{};
         }
       }
     }
