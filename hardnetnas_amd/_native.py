@@ -55,7 +55,8 @@ EXPORTED = ["hn_param_count", "hn_create", "hn_workspace_bytes", "hn_forward",
             "hn_nas_train_tensor_count", "hn_nas_train_workspace_bytes", "hn_nas_train_forward",
             "hn_nas_train_backward", "hn_hardnet_loss_train_workspace_bytes", "hn_hardnet_loss_train_forward",
             "hn_hardnet_loss_backward", "hn_fpr95_workspace_bytes",
-            "hn_fpr95", "hn_match_workspace_bytes", "hn_match_nn2", "hn_preprocess", "hn_set_profiling",
+            "hn_fpr95", "hn_match_workspace_bytes", "hn_match_nn2", "hn_clip_patch", "hn_workspace_bytes_kp",
+            "hn_forward_kp", "hn_preprocess", "hn_set_profiling",
             "hn_stage_times", "hn_destroy", "hn_last_error", "hn_abi_version"]
 
 
@@ -107,6 +108,9 @@ def load_library():
         lib.hn_fpr95.argtypes = [P, P, P, I64, I32, P, P, P, S, P]
         lib.hn_match_workspace_bytes.argtypes = [I64, I64, ctypes.POINTER(S)]
         lib.hn_match_nn2.argtypes = [P, I64, P, I64, I32, I32, P, P, P, S, P]
+        lib.hn_clip_patch.argtypes = [P, I64, I32, I32, P, P, P, P, I64, P, P]
+        lib.hn_workspace_bytes_kp.argtypes = [P, I64, ctypes.POINTER(S)]
+        lib.hn_forward_kp.argtypes = [P, P, I64, I32, I32, P, P, P, P, I64, P, P, S, P]
         lib.hn_preprocess.argtypes = [P, I64, I32, I32, I32, ctypes.c_float, ctypes.c_float, P, P]
         lib.hn_set_profiling.argtypes = [P, ctypes.c_int]
         lib.hn_stage_times.argtypes = [P, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p),
@@ -123,7 +127,7 @@ def load_library():
                      "hn_hardnet_train_backward", "hn_nas_train_tensor_count", "hn_nas_train_workspace_bytes",
                      "hn_nas_train_forward", "hn_nas_train_backward", "hn_hardnet_loss_train_workspace_bytes",
                      "hn_hardnet_loss_train_forward", "hn_hardnet_loss_backward", "hn_match_workspace_bytes",
-                     "hn_match_nn2"):
+                     "hn_match_nn2", "hn_clip_patch", "hn_workspace_bytes_kp", "hn_forward_kp"):
             getattr(lib, name).restype = ctypes.c_int
         if lib.hn_abi_version() != ABI_VERSION:
             raise RuntimeError(f"{path}: ABI version {lib.hn_abi_version()}, expected {ABI_VERSION}; rebuild it")
@@ -296,6 +300,37 @@ class NativeModel:
         n = ctypes.c_size_t()
         _check(self.lib.hn_workspace_bytes_u8(self._h, batch, ctypes.byref(n)), "hn_workspace_bytes_u8")
         return n.value
+
+    def workspace_bytes_kp(self, n: int) -> int:
+        sz = ctypes.c_size_t()
+        _check(self.lib.hn_workspace_bytes_kp(self._h, n, ctypes.byref(sz)), "hn_workspace_bytes_kp")
+        return sz.value
+
+    def forward_keypoints(self, images: torch.Tensor, kpts: torch.Tensor, scale: torch.Tensor,
+                          ori: Optional[torch.Tensor], ratio: torch.Tensor, out: Optional[torch.Tensor] = None,
+                          workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Descriptors [N,128] of keypoints (arguments as ``clip_patch``): the patches are clipped into the
+        workspace a chunk at a time and never leave it -- equal to ``forward(clip_patch(...))`` bit for bit."""
+        im, kp, sc, orr, ra = _keypoint_args(images, kpts, scale, ori, ratio, self.device)
+        n = kp.shape[0]
+        if out is None:
+            out = torch.empty((n, 128), device=self.device, dtype=torch.float32)
+        elif (tuple(out.shape) != (n, 128) or out.dtype != torch.float32 or out.device != self.device
+              or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous fp32 [{n},128] tensor on {self.device}")
+        need = self.workspace_bytes_kp(n)
+        if workspace is not None and (workspace.dtype != torch.uint8 or workspace.device != self.device
+                                      or not workspace.is_contiguous()):
+            raise ValueError(f"workspace must be a contiguous uint8 tensor on {self.device}")
+        if workspace is None or workspace.numel() < need:
+            workspace = torch.empty(max(need, 16), device=self.device, dtype=torch.uint8)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        with torch.cuda.device(self.device):
+            _check(self.lib.hn_forward_kp(self._h, im.data_ptr(), im.shape[0], im.shape[2], im.shape[3],
+                                          kp.data_ptr(), sc.data_ptr(), orr.data_ptr() if orr is not None else None,
+                                          ra.data_ptr(), n, out.data_ptr(), workspace.data_ptr(), workspace.numel(),
+                                          stream), "hn_forward_kp")
+        return out
 
     def set_profiling(self, on: bool):
         _check(self.lib.hn_set_profiling(self._h, int(on)), "hn_set_profiling")
@@ -501,6 +536,55 @@ def match_nn2(query: torch.Tensor, db: torch.Tensor, metric: str = "unit",
         _check(lib.hn_match_nn2(q.data_ptr(), n, b.data_ptr(), m, d, MATCH_METRICS[metric], dist.data_ptr(),
                                 idx.data_ptr(), workspace.data_ptr(), workspace.numel(), stream), "hn_match_nn2")
     return dist, idx
+
+
+def _keypoint_args(images, kpts, scale, ori, ratio, device=None):
+    """The validated, contiguous (images, kpts, scale, ori or None, ratio) of hn_clip_patch / hn_forward_kp."""
+    dev = images.device if device is None else device
+    if not images.is_cuda or images.device != dev:
+        raise ValueError(f"images must be a HIP tensor on {dev}, got {images.device}")
+    if images.dtype != torch.float32 or images.dim() != 4 or images.shape[1] != 1:
+        raise ValueError(f"images must be fp32 [B,1,H,W], got {images.dtype} {tuple(images.shape)}")
+    b, _, h, w = images.shape
+    if b < 1 or h < 2 or w < 2:
+        raise ValueError(f"images must hold at least one image of at least 2x2 pixels, got {tuple(images.shape)}")
+    if kpts.dtype != torch.int64 or kpts.dim() != 2 or kpts.shape[1] != 4 or kpts.device != dev:
+        raise ValueError(f"kpts must be int64 [N,4] rows (b, y, x, .) on {dev}, got {kpts.dtype} "
+                         f"{tuple(kpts.shape)} on {kpts.device}")
+    n = kpts.shape[0]
+    if scale.dtype != torch.float32 or scale.numel() != n or scale.device != dev:
+        raise ValueError(f"scale must be fp32 [{n}] on {dev}, got {scale.dtype} {tuple(scale.shape)} on {scale.device}")
+    if ori is not None and (ori.dtype != torch.float32 or tuple(ori.shape) != (n, 2) or ori.device != dev):
+        raise ValueError(f"ori must be None or fp32 [{n},2] (cos, sin) on {dev}, got {ori.dtype} "
+                         f"{tuple(ori.shape)} on {ori.device}")
+    if ratio.dtype != torch.float32 or ratio.numel() != b or ratio.device != dev:
+        raise ValueError(f"ratio must be fp32 [{b}] (im_info[:,0]) on {dev}, got {ratio.dtype} "
+                         f"{tuple(ratio.shape)} on {ratio.device}")
+    return (images.contiguous(), kpts.contiguous(), scale.contiguous().view(-1),
+            ori.contiguous() if ori is not None else None, ratio.contiguous().view(-1))
+
+
+def clip_patch(images: torch.Tensor, kpts: torch.Tensor, scale: torch.Tensor, ori: Optional[torch.Tensor],
+               ratio: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Rotated, scaled 32x32 windows around keypoints, FDLNet's clip_patch (utils/image_utils.py:11-158) in one
+    kernel: images fp32 [B,1,H,W], kpts int64 [N,4] rows (b, y, x, .), scale fp32 [N], ori fp32 [N,2] (cos, sin)
+    or None, ratio fp32 [B] (im_info[:,0]), all on one HIP device -> fp32 [N,1,32,32].  Column 0 of a keypoint
+    selects its image and its ratio; the call reads nothing outside ``images`` whatever the keypoint data
+    (include/hardnet_mi355x.h)."""
+    lib = load_library()
+    im, kp, sc, orr, ra = _keypoint_args(images, kpts, scale, ori, ratio)
+    n = kp.shape[0]
+    if out is None:
+        out = torch.empty((n, 1, 32, 32), device=im.device, dtype=torch.float32)
+    elif (tuple(out.shape) != (n, 1, 32, 32) or out.dtype != torch.float32 or out.device != im.device
+          or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous fp32 [{n},1,32,32] tensor on {im.device}")
+    stream = torch.cuda.current_stream(im.device).cuda_stream
+    with torch.cuda.device(im.device):
+        _check(lib.hn_clip_patch(im.data_ptr(), im.shape[0], im.shape[2], im.shape[3], kp.data_ptr(), sc.data_ptr(),
+                                 orr.data_ptr() if orr is not None else None, ra.data_ptr(), n, out.data_ptr(),
+                                 stream), "hn_clip_patch")
+    return out
 
 
 RESIZE_MODES = {"none": 0, "cv2": 1, "pil": 2}  # enum hn_resize

@@ -1378,6 +1378,71 @@ extern "C" int hn_forward_u8(hn_model* m, const uint8_t* d_in, int64_t batch, in
   return HN_OK;
 }
 
+// keypoint patch extraction (hn_clip.hip): what hn_clip_patch and hn_forward_kp check about the images and
+// the keypoint list before the GPU is touched; null = fine
+static const char* clip_arg_error(int64_t n_images, int32_t height, int32_t width, int64_t n) {
+  if (n < 0) return "n must be >= 0";
+  if (n_images < 0) return "n_images must be >= 0";
+  if (height < 2 || width < 2) return "height and width must be >= 2";
+  // n_images * height * width < 2^63: the flat index of every pixel fits an int64
+  if (n_images > INT64_MAX / ((int64_t)height * (int64_t)width)) return "n_images * height * width must be below 2^63";
+  if (n > 0 && n_images == 0) return "n_images must be >= 1 for n > 0 keypoints";
+  return nullptr;
+}
+
+extern "C" int hn_clip_patch(const float* d_images, int64_t n_images, int32_t height, int32_t width,
+                             const int64_t* d_kpts, const float* d_scale, const float* d_ori, const float* d_ratio,
+                             int64_t n, float* d_patches, void* hip_stream) {
+  if (const char* e = clip_arg_error(n_images, height, width, n)) return fail(HN_ERR_ARG, e);
+  if (n == 0) return HN_OK;
+  if (!d_images || !d_kpts || !d_scale || !d_ratio || !d_patches)
+    return fail(HN_ERR_ARG, "NULL device pointer (only d_ori may be NULL)");
+  if (reinterpret_cast<uintptr_t>(d_patches) & 15) return fail(HN_ERR_ARG, "d_patches must be 16-byte aligned");
+  HIPCHK(hn_launch_clip(d_images, n_images, height, width, d_kpts, d_scale, d_ori, d_ratio, n, d_patches,
+                        static_cast<hipStream_t>(hip_stream)));
+  return HN_OK;
+}
+
+extern "C" int hn_workspace_bytes_kp(const hn_model* m, int64_t n, size_t* bytes_out) {
+  int rc = hn_workspace_bytes(m, n, bytes_out);
+  if (rc) return rc;
+  *bytes_out += (size_t)std::min<int64_t>(n, m->chunk) * 1024 * sizeof(float);  // a chunk's fp32 patches
+  return HN_OK;
+}
+
+// Descriptors of keypoints: each chunk's patches clipped into the workspace tail, then the model's forward on
+// them (hn_forward_u8's unfused branch with hn_launch_clip in hn_launch_preprocess's place).
+extern "C" int hn_forward_kp(hn_model* m, const float* d_images, int64_t n_images, int32_t height, int32_t width,
+                             const int64_t* d_kpts, const float* d_scale, const float* d_ori, const float* d_ratio,
+                             int64_t n, float* d_out, void* d_workspace, size_t workspace_bytes, void* hip_stream) {
+  if (const char* e = clip_arg_error(n_images, height, width, n)) return fail(HN_ERR_ARG, e);
+  if (!m) return fail(HN_ERR_ARG, "model is NULL");
+  if (n == 0) return HN_OK;
+  if (!d_images || !d_kpts || !d_scale || !d_ratio || !d_out || !d_workspace)
+    return fail(HN_ERR_ARG, "NULL device pointer (only d_ori may be NULL)");
+  if ((reinterpret_cast<uintptr_t>(d_out) | reinterpret_cast<uintptr_t>(d_workspace)) & 15)
+    return fail(HN_ERR_ARG, "d_out / d_workspace must be 16-byte aligned");
+  size_t need = 0, base = 0;
+  hn_workspace_bytes_kp(m, n, &need);
+  if (workspace_bytes < need)
+    return fail(HN_ERR_WORKSPACE, "workspace too small: need " + std::to_string(need) + " bytes");
+  hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  KnobScope knobs(&m->knobs);
+  float* ws = static_cast<float*>(d_workspace);
+  hn_workspace_bytes(m, n, &base);
+  float* patches = reinterpret_cast<float*>(static_cast<char*>(d_workspace) + base);
+  const int pmax = (int)std::min<int64_t>(m->chunk, n);
+  for (int64_t off = 0; off < n; off += m->chunk) {
+    const int P = (int)std::min<int64_t>(m->chunk, n - off);
+    STAGE("clip", hn_launch_clip(d_images, n_images, height, width, d_kpts + off * 4, d_scale + off,
+                                 d_ori ? d_ori + off * 2 : nullptr, d_ratio, P, patches, st));
+    const int rc = m->desc.kind == HN_KIND_HARDNET ? forward_hardnet(m, patches, P, pmax, d_out + off * 128, ws, st)
+                                                   : forward_nas(m, patches, P, pmax, d_out + off * 128, ws, st);
+    if (rc) return rc;
+  }
+  return HN_OK;
+}
+
 // ---------------------------------------------------------------------------------------
 // train-mode stock HardNet (hn_train.hip)
 // ---------------------------------------------------------------------------------------

@@ -222,6 +222,10 @@ hipError_t hn_launch_split_planes(const float* p, int B, uint16_t* ph, uint16_t*
 size_t hn_match_ws_bytes(long N, long M);
 hipError_t hn_launch_match_nn2(const float* q, int N, const float* db, int M, int metric, float* dist, int* idx,
                                void* ws, hipStream_t st);
+// rotated, scaled 32x32 windows around keypoints (b, y, x, .) of images [B,1,H,W] (hn_clip.hip): out [n,1,32,32];
+// ori null: no rotation.  Reads nothing outside images whatever the keypoint data (B >= 1, H, W >= 2)
+hipError_t hn_launch_clip(const float* images, int64_t B, int H, int W, const int64_t* kpts, const float* scale,
+                          const float* ori, const float* ratio, int64_t n, float* out, hipStream_t st);
 hipError_t hn_launch_loss(const float* pos, const float* rmin, const float* cmin, int n, float margin,
                           int type, float scale, float* min_neg, float* loss, hipStream_t st);
 

@@ -234,6 +234,44 @@ int hn_forward_u8(hn_model* m, const uint8_t* d_in, int64_t batch, int32_t in_hw
                   int32_t normalize, float mean, float std, float* d_out, void* d_workspace,
                   size_t workspace_bytes, void* hip_stream);
 
+/* Keypoint patch extraction, the step between FDLNet's detector and its descriptor (clip_patch,
+ * FDLNet-master/latency/NASNet/utils/image_utils.py:11-158, as model/network.py:163-176 calls it): a rotated,
+ * scaled 32x32 window around every keypoint, sampled from its image by bilinear interpolation.
+ *   d_images [n_images,1,height,width] fp32 contiguous; d_kpts [n,4] int64 rows (b, y, x, .) as nonzero()
+ *   gives them; d_scale [n] fp32; d_ori [n,2] fp32 (cos, sin), or NULL for no rotation; d_ratio [n_images]
+ *   fp32 (im_info[:,0]); d_patches [n,1,32,32] fp32 (16-byte aligned).
+ * Arithmetic: the reference's, in fp32 and in its operation order, with IEEE division and no fused multiply-add:
+ *   r = ratio[b]; s = (scale / r) / 2; kx = float(x) / r; ky = float(y) / r;
+ *   g[i] = torch.linspace(-1, 1, 32)[i] (step 2/31: -1 + step i for i < 16, else 1 - step (31 - i));
+ *   xs = (s cos) g[col] + (-(s sin)) g[row] + kx;  ys = (s sin) g[col] + (s cos) g[row] + ky;
+ *   x0 = floor(xs), x1 = x0 + 1, both clamped to [0, width - 1]; y0, y1 likewise with height - 1;
+ *   the four weights (x1 - xs)(y1 - ys), (x1 - xs)(ys - y0), (xs - x0)(y1 - ys), (xs - x0)(ys - y0) use the
+ *   CLAMPED corners converted back to float, which is what makes a sample outside the image come out (nearly)
+ *   zero; out = wa Ia + wb Ib + wc Ic + wd Id, summed left to right.
+ * Bounds guarantee: the call reads no byte outside d_images whatever the keypoint data.  The batch index is
+ * clamped to [0, n_images - 1] for addressing (image and ratio); NaN, +-Inf and coordinates beyond the integer
+ * range are made safe before the float -> integer conversion.  The patch of such a keypoint is unspecified; every
+ * other keypoint's patch is unaffected, and a keypoint's patch never depends on which others share the call.
+ * One deliberate difference from the reference: the reference maps keypoint i to ratio row i / (n / n_images)
+ * (a .view(B, -1)) but to its image through the keypoint's own column 0, which agree only when every image
+ * has the same number of keypoints, in batch order.  Here column 0 selects both, so unequal counts per image and
+ * any keypoint order work; where the reference is consistent the results are the same.
+ * No allocation or synchronisation inside; every argument check runs before the GPU is touched: n, n_images
+ * >= 0 (n == 0 returns HN_OK; n > 0 needs n_images >= 1), height, width >= 2, n_images * height * width < 2^63. */
+int hn_clip_patch(const float* d_images, int64_t n_images, int32_t height, int32_t width, const int64_t* d_kpts,
+                  const float* d_scale, const float* d_ori, const float* d_ratio, int64_t n, float* d_patches,
+                  void* hip_stream);
+
+/* Descriptors of keypoints: hn_clip_patch into the workspace tail, a chunk of min(n, chunk) keypoints at a
+ * time, then the model's forward on the chunk.  Equals hn_clip_patch followed by hn_forward bit for bit, for
+ * every model kind; d_out [n,128] fp32.  Workspace: hn_workspace_bytes_kp = hn_workspace_bytes + min(n, chunk)
+ * x 4 KiB; a short one is HN_ERR_WORKSPACE.  d_out and d_workspace 16-byte aligned.  Capturable like hn_forward.
+ * (The sampling is not fused into the first kernel's patch load the way the uint8 path is.) */
+int hn_workspace_bytes_kp(const hn_model* m, int64_t n, size_t* bytes_out);
+int hn_forward_kp(hn_model* m, const float* d_images, int64_t n_images, int32_t height, int32_t width,
+                  const int64_t* d_kpts, const float* d_scale, const float* d_ori, const float* d_ratio, int64_t n,
+                  float* d_out, void* d_workspace, size_t workspace_bytes, void* hip_stream);
+
 /* Train-mode stock HardNet (the module of hardnet/HardNet.py:275-315 in
  * model.train() as the training loop :379-441 runs it through autograd).
  *  forward : input_norm (mean / std detached), 7 x [conv -> BatchNorm2d(affine=False) with the
