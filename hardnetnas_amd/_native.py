@@ -56,7 +56,8 @@ EXPORTED = ["hn_param_count", "hn_create", "hn_workspace_bytes", "hn_forward",
             "hn_nas_train_backward", "hn_hardnet_loss_train_workspace_bytes", "hn_hardnet_loss_train_forward",
             "hn_hardnet_loss_backward", "hn_fpr95_workspace_bytes",
             "hn_fpr95", "hn_match_workspace_bytes", "hn_match_nn2", "hn_clip_patch", "hn_workspace_bytes_kp",
-            "hn_forward_kp", "hn_preprocess", "hn_set_profiling",
+            "hn_forward_kp", "hn_det_param_count", "hn_det_create", "hn_det_workspace_bytes", "hn_det_forward",
+            "hn_det_destroy", "hn_select_workspace_bytes", "hn_select_keypoints", "hn_preprocess", "hn_set_profiling",
             "hn_stage_times", "hn_destroy", "hn_last_error", "hn_abi_version"]
 
 
@@ -111,6 +112,16 @@ def load_library():
         lib.hn_clip_patch.argtypes = [P, I64, I32, I32, P, P, P, P, I64, P, P]
         lib.hn_workspace_bytes_kp.argtypes = [P, I64, ctypes.POINTER(S)]
         lib.hn_forward_kp.argtypes = [P, P, I64, I32, I32, P, P, P, P, I64, P, P, S, P]
+        F32 = ctypes.c_float
+        lib.hn_det_param_count.argtypes = [ctypes.POINTER(S)]
+        lib.hn_det_create.argtypes = [P, S, F32, F32, ctypes.POINTER(P)]
+        lib.hn_det_workspace_bytes.argtypes = [I64, I32, I32, ctypes.POINTER(S)]
+        lib.hn_det_forward.argtypes = [P, P, I64, I32, I32, P, P, P, S, P]
+        lib.hn_det_destroy.argtypes = [P]
+        lib.hn_det_destroy.restype = None
+        lib.hn_select_workspace_bytes.argtypes = [I64, I32, I32, I32, ctypes.POINTER(S)]
+        lib.hn_select_keypoints.argtypes = [P, I64, I32, I32, I32, F32, I32, I32, I32, F32, P, F32, P, P, P, P, P, P, P,
+                                            P, S, P]
         lib.hn_preprocess.argtypes = [P, I64, I32, I32, I32, ctypes.c_float, ctypes.c_float, P, P]
         lib.hn_set_profiling.argtypes = [P, ctypes.c_int]
         lib.hn_stage_times.argtypes = [P, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p),
@@ -127,7 +138,9 @@ def load_library():
                      "hn_hardnet_train_backward", "hn_nas_train_tensor_count", "hn_nas_train_workspace_bytes",
                      "hn_nas_train_forward", "hn_nas_train_backward", "hn_hardnet_loss_train_workspace_bytes",
                      "hn_hardnet_loss_train_forward", "hn_hardnet_loss_backward", "hn_match_workspace_bytes",
-                     "hn_match_nn2", "hn_clip_patch", "hn_workspace_bytes_kp", "hn_forward_kp"):
+                     "hn_match_nn2", "hn_clip_patch", "hn_workspace_bytes_kp", "hn_forward_kp",
+                     "hn_det_param_count", "hn_det_create", "hn_det_workspace_bytes", "hn_det_forward",
+                     "hn_select_workspace_bytes", "hn_select_keypoints"):
             getattr(lib, name).restype = ctypes.c_int
         if lib.hn_abi_version() != ABI_VERSION:
             raise RuntimeError(f"{path}: ABI version {lib.hn_abi_version()}, expected {ABI_VERSION}; rebuild it")
@@ -584,6 +597,126 @@ def clip_patch(images: torch.Tensor, kpts: torch.Tensor, scale: torch.Tensor, or
         _check(lib.hn_clip_patch(im.data_ptr(), im.shape[0], im.shape[2], im.shape[3], kp.data_ptr(), sc.data_ptr(),
                                  orr.data_ptr() if orr is not None else None, ra.data_ptr(), n, out.data_ptr(),
                                  stream), "hn_clip_patch")
+    return out
+
+
+class NativeDetector:
+    """FDLNet's NASNet keypoint detector on the device (hn_det_create): ``blob`` is ``state_dict_blob`` of an
+    ``RFDet.state_dict()`` -- features.0.{weight,bias}; per InvertedResidual banch2.0.weight, banch2.1.{weight,
+    bias,running_mean,running_var}, banch2.3.weight, banch2.4.{..}, banch2.5.weight, banch2.6.{..};
+    conv.{weight,bias}; insnorm.{weight,bias}; conv_ori.{weight,bias}; insnorm_ori.{weight,bias}."""
+
+    def __init__(self, blob: np.ndarray, device, bn_eps: float = 1e-5, in_eps: float = 1e-5):
+        self.lib = load_library()
+        self.device = torch.device(device)
+        n = ctypes.c_size_t()
+        _check(self.lib.hn_det_param_count(ctypes.byref(n)), "hn_det_param_count")
+        if n.value != blob.size:
+            raise ValueError(f"parameter blob has {blob.size} floats, library expects {n.value}")
+        h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _check(self.lib.hn_det_create(blob.ctypes.data, blob.size, bn_eps, in_eps, ctypes.byref(h)),
+                   "hn_det_create")
+        self._h = h
+        self._ws = None  # workspace cache: grows, never shrinks
+
+    def workspace_bytes(self, n_images: int, height: int, width: int) -> int:
+        n = ctypes.c_size_t()
+        _check(self.lib.hn_det_workspace_bytes(n_images, height, width, ctypes.byref(n)), "hn_det_workspace_bytes")
+        return n.value
+
+    def forward(self, images: torch.Tensor, score: Optional[torch.Tensor] = None, ori: Optional[torch.Tensor] = None,
+                workspace: Optional[torch.Tensor] = None):
+        """images fp32 [B,1,H,W] -> (score [B,H,W], ori [B,H,W,2]).  The workspace is cached on the object (or
+        pass one of at least workspace_bytes(B, H, W) bytes, as under graph capture of several shapes)."""
+        if images.device != self.device or images.dtype != torch.float32 or images.dim() != 4 or images.shape[1] != 1:
+            raise ValueError(f"expected fp32 [B,1,H,W] on {self.device}, got {images.dtype} {tuple(images.shape)} "
+                             f"on {images.device}")
+        x = images.contiguous()
+        b, _, h, w = x.shape
+        if score is None:
+            score = torch.empty((b, h, w), device=self.device, dtype=torch.float32)
+        if ori is None:
+            ori = torch.empty((b, h, w, 2), device=self.device, dtype=torch.float32)
+        for t, shp in ((score, (b, h, w)), (ori, (b, h, w, 2))):
+            if tuple(t.shape) != shp or t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous():
+                raise ValueError(f"outputs must be contiguous fp32 {shp} tensors on {self.device}")
+        need = self.workspace_bytes(b, h, w)
+        if workspace is None:
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = torch.empty(max(need, 16), device=self.device, dtype=torch.uint8)
+            workspace = self._ws
+        elif workspace.dtype != torch.uint8 or workspace.device != self.device or not workspace.is_contiguous():
+            raise ValueError(f"workspace must be a contiguous uint8 tensor on {self.device}")
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        with torch.cuda.device(self.device):
+            _check(self.lib.hn_det_forward(self._h, x.data_ptr(), b, h, w, score.data_ptr(), ori.data_ptr(),
+                                           workspace.data_ptr(), workspace.numel(), stream), "hn_det_forward")
+        return score, ori
+
+    __call__ = forward
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self.lib.hn_det_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def select_workspace_bytes(n_images: int, height: int, width: int, topk: int) -> int:
+    n = ctypes.c_size_t()
+    _check(load_library().hn_select_workspace_bytes(n_images, height, width, topk, ctypes.byref(n)),
+           "hn_select_workspace_bytes")
+    return n.value
+
+
+def select_keypoints(score: torch.Tensor, border: int, nms_thresh: float, nms_ksize: int, topk: int,
+                     gauss_ksize: int, gauss_sigma: float, scale_map: Optional[torch.Tensor] = None,
+                     scale_value: float = 32.0, ori_map: Optional[torch.Tensor] = None, dense: bool = False,
+                     workspace: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """Keypoints of a score map [B,H,W] (fp32, HIP): RFDet.process + the second top-K + nonzero() + gathers
+    (hn_select_keypoints, include/hardnet_mi355x.h).  Returns ``kpts`` [B K,4] int64 rows (b, y, x, 0) in raster
+    order per image, ``kscore`` (the raw score), ``kscale`` (from ``scale_map`` [B,H,W] or ``scale_value``),
+    ``kori`` [B K,2] from ``ori_map`` [B,H,W,2] (or None), and with ``dense`` also ``score_proc`` [B,H,W] and
+    ``topk_mask`` [B,H,W] uint8.  Ties at both top-K steps go to the lowest flat index; NaN counts as 0."""
+    lib = load_library()
+    if not score.is_cuda or score.dtype != torch.float32 or score.dim() != 3:
+        raise ValueError(f"score must be a fp32 HIP tensor [B,H,W], got {score.dtype} {tuple(score.shape)}")
+    dev = score.device
+    s = score.contiguous()
+    b, h, w = s.shape
+    for name, t, shp in (("scale_map", scale_map, (b, h, w)), ("ori_map", ori_map, (b, h, w, 2))):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != shp or t.device != dev):
+            raise ValueError(f"{name} must be fp32 {shp} on {dev}")
+    sm = scale_map.contiguous() if scale_map is not None else None
+    om = ori_map.contiguous() if ori_map is not None else None
+    need = select_workspace_bytes(b, h, w, topk)
+    if workspace is not None and (workspace.dtype != torch.uint8 or workspace.device != dev
+                                  or not workspace.is_contiguous()):
+        raise ValueError(f"workspace must be a contiguous uint8 tensor on {dev}")
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 16), device=dev, dtype=torch.uint8)
+    n = b * topk
+    out = {"kpts": torch.empty((n, 4), device=dev, dtype=torch.int64),
+           "kscore": torch.empty(n, device=dev, dtype=torch.float32),
+           "kscale": torch.empty(n, device=dev, dtype=torch.float32),
+           "kori": torch.empty((n, 2), device=dev, dtype=torch.float32) if om is not None else None}
+    if dense:
+        out["score_proc"] = torch.empty((b, h, w), device=dev, dtype=torch.float32)
+        out["topk_mask"] = torch.empty((b, h, w), device=dev, dtype=torch.uint8)
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        _check(lib.hn_select_keypoints(s.data_ptr(), b, h, w, border, nms_thresh, nms_ksize, topk, gauss_ksize,
+                                       gauss_sigma, ptr(sm), scale_value, ptr(om), out["kpts"].data_ptr(),
+                                       out["kscore"].data_ptr(), out["kscale"].data_ptr(), ptr(out["kori"]),
+                                       ptr(out.get("score_proc")), ptr(out.get("topk_mask")), workspace.data_ptr(),
+                                       workspace.numel(), stream), "hn_select_keypoints")
     return out
 
 

@@ -1444,6 +1444,202 @@ extern "C" int hn_forward_kp(hn_model* m, const float* d_images, int64_t n_image
 }
 
 // ---------------------------------------------------------------------------------------
+// FDLNet's NASNet keypoint detector (hn_det.hip) and keypoint selection (hn_select.hip)
+// ---------------------------------------------------------------------------------------
+struct hn_detector {
+  float* params = nullptr;  // hndet layout, BN folded
+  float in_eps = 1e-5f;
+};
+
+extern "C" int hn_det_param_count(size_t* n_out) {
+  if (!n_out) return fail(HN_ERR_ARG, "n_out is NULL");
+  *n_out = hndet::kStateFloats;
+  return HN_OK;
+}
+
+extern "C" int hn_det_create(const float* host_params, size_t n_params, float bn_eps, float in_eps,
+                             hn_detector** out) {
+  using namespace hndet;
+  if (!out || !host_params) return fail(HN_ERR_ARG, "NULL argument");
+  *out = nullptr;
+  if (n_params != (size_t)kStateFloats)
+    return fail(HN_ERR_ARG, "host_params has " + std::to_string(n_params) + " floats, expected " +
+                                std::to_string(kStateFloats));
+  if (!(bn_eps > 0.f) || !(in_eps > 0.f)) return fail(HN_ERR_ARG, "bn_eps and in_eps must be > 0");
+  for (size_t i = 0; i < n_params; ++i)
+    if (!std::isfinite(host_params[i])) return fail(HN_ERR_ARG, "host_params holds a non-finite value");
+  std::vector<float> f(kFolded);
+  const float* p = host_params;
+  std::memcpy(&f[kC0W], p, 160 * sizeof(float));  // features.0.weight, .bias
+  p += 160;
+  // conv weight [cout][per] without bias, then BatchNorm weight, bias, running_mean, running_var [cout]
+  auto conv_bn = [&](int cout, int per, float* w, float* b) -> bool {
+    const float *cw = p, *g = p + cout * per, *be = g + cout, *rm = be + cout, *rv = rm + cout;
+    p = rv + cout;
+    for (int o = 0; o < cout; ++o) {
+      if (!((double)rv[o] + bn_eps > 0)) return false;
+      const double s = (double)g[o] / std::sqrt((double)rv[o] + (double)bn_eps);
+      for (int k = 0; k < per; ++k) w[o * per + k] = (float)((double)cw[o * per + k] * s);
+      b[o] = (float)((double)be[o] - (double)rm[o] * s);
+    }
+    return true;
+  };
+  for (int k = 0; k < 2; ++k) {
+    float* blk = &f[kBlk + k * kBlkSize];
+    if (!conv_bn(8, 8, blk + kBlkPw1W, blk + kBlkPw1B) || !conv_bn(8, 9, blk + kBlkDwW, blk + kBlkDwB) ||
+        !conv_bn(8, 8, blk + kBlkPw2W, blk + kBlkPw2B))
+      return fail(HN_ERR_ARG, "a BatchNorm running_var + bn_eps is not positive");
+  }
+  std::memcpy(&f[kHeadW], p, 144 * sizeof(float));  // conv.weight
+  f[kHeadB] = p[144];                               // conv.bias
+  f[kInG] = p[145];                                 // insnorm.weight, .bias
+  f[kInB] = p[146];
+  p += 147;
+  std::memcpy(&f[kHeadW + 144], p, 288 * sizeof(float));  // conv_ori.weight
+  f[kHeadB + 1] = p[288];                                 // conv_ori.bias
+  f[kHeadB + 2] = p[289];
+  f[kInG + 1] = p[290];                                   // insnorm_ori.weight, .bias
+  f[kInG + 2] = p[291];
+  f[kInB + 1] = p[292];
+  f[kInB + 2] = p[293];
+  p += 294;
+  if ((size_t)(p - host_params) != n_params) return fail(HN_ERR_ARG, "host_params not fully consumed");
+  hn_detector* d = new hn_detector;
+  d->in_eps = in_eps;
+  if (hipMalloc(&d->params, kFolded * sizeof(float)) != hipSuccess) {
+    delete d;
+    return fail(HN_ERR_NOMEM, "hipMalloc of parameters failed");
+  }
+  const hipError_t e = hipMemcpy(d->params, f.data(), kFolded * sizeof(float), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(d->params);
+    delete d;
+    return fail(HN_ERR_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
+  }
+  *out = d;
+  return HN_OK;
+}
+
+extern "C" void hn_det_destroy(hn_detector* d) {
+  if (!d) return;
+  (void)hipFree(d->params);
+  delete d;
+}
+
+// what hn_det_workspace_bytes and hn_det_forward check about the images; null = fine
+static const char* det_arg_error(int64_t n_images, int32_t height, int32_t width) {
+  if (n_images < 0) return "n_images must be >= 0";
+  if (height < 1 || width < 1 || (int64_t)height * width < 2)
+    return "height and width must be >= 1 with at least 2 pixels (InstanceNorm)";
+  if ((int64_t)height * width > INT32_MAX) return "height * width must be below 2^31";
+  if (n_images > INT32_MAX || n_images * hn_det_parts(height, width) > INT32_MAX)
+    return "n_images * tiles must be below 2^31";
+  return nullptr;
+}
+
+extern "C" int hn_det_workspace_bytes(int64_t n_images, int32_t height, int32_t width, size_t* bytes_out) {
+  if (!bytes_out) return fail(HN_ERR_ARG, "bytes_out is NULL");
+  if (const char* e = det_arg_error(n_images, height, width)) return fail(HN_ERR_ARG, e);
+  *bytes_out = hn_det_ws_bytes(n_images, height, width);
+  return HN_OK;
+}
+
+extern "C" int hn_det_forward(hn_detector* d, const float* d_images, int64_t n_images, int32_t height, int32_t width,
+                              float* d_score, float* d_ori, void* d_workspace, size_t workspace_bytes,
+                              void* hip_stream) {
+  if (const char* e = det_arg_error(n_images, height, width)) return fail(HN_ERR_ARG, e);
+  if (!d) return fail(HN_ERR_ARG, "detector is NULL");
+  if (n_images == 0) return HN_OK;
+  if (!d_images || !d_score || !d_ori || !d_workspace) return fail(HN_ERR_ARG, "NULL device pointer");
+  if ((reinterpret_cast<uintptr_t>(d_ori) & 7) || (reinterpret_cast<uintptr_t>(d_workspace) & 15))
+    return fail(HN_ERR_ARG, "d_ori must be 8-byte and d_workspace 16-byte aligned");
+  const size_t need = hn_det_ws_bytes(n_images, height, width);
+  if (workspace_bytes < need)
+    return fail(HN_ERR_WORKSPACE, "workspace too small: need " + std::to_string(need) + " bytes");
+  HIPCHK(hn_launch_det(d->params, d->in_eps, d_images, n_images, height, width, d_score, d_ori, d_workspace,
+                       static_cast<hipStream_t>(hip_stream)));
+  return HN_OK;
+}
+
+// what hn_select_workspace_bytes and hn_select_keypoints check about the map and K; null = fine
+static const char* select_arg_error(int64_t n_images, int32_t height, int32_t width, int32_t topk) {
+  if (n_images < 0) return "n_images must be >= 0";
+  if (height < 1 || width < 1) return "height and width must be >= 1";
+  if ((int64_t)height * width > INT32_MAX) return "height * width must be below 2^31";
+  if (n_images > INT32_MAX) return "n_images must be below 2^31";
+  if (topk < 1 || topk > (int64_t)height * width) return "topk must be in 1 .. height * width";
+  return nullptr;
+}
+
+extern "C" int hn_select_workspace_bytes(int64_t n_images, int32_t height, int32_t width, int32_t topk,
+                                         size_t* bytes_out) {
+  if (!bytes_out) return fail(HN_ERR_ARG, "bytes_out is NULL");
+  if (const char* e = select_arg_error(n_images, height, width, topk)) return fail(HN_ERR_ARG, e);
+  *bytes_out = hn_select_ws_bytes(n_images, height, width);
+  return HN_OK;
+}
+
+extern "C" int hn_select_keypoints(const float* d_score, int64_t n_images, int32_t height, int32_t width,
+                                   int32_t border, float nms_thresh, int32_t nms_ksize, int32_t topk,
+                                   int32_t gauss_ksize, float gauss_sigma, const float* d_scale_map,
+                                   float scale_value, const float* d_ori_map, int64_t* d_kpts, float* d_kscore,
+                                   float* d_kscale, float* d_kori, float* d_score_proc, uint8_t* d_topk_mask,
+                                   void* d_workspace, size_t workspace_bytes, void* hip_stream) {
+  if (const char* e = select_arg_error(n_images, height, width, topk)) return fail(HN_ERR_ARG, e);
+  if (border < 0 || height <= 2 * (int64_t)border || width <= 2 * (int64_t)border)
+    return fail(HN_ERR_ARG, "border must be >= 0 with height, width > 2 * border");
+  if (nms_ksize < 1 || nms_ksize > 15 || !(nms_ksize & 1)) return fail(HN_ERR_ARG, "nms_ksize must be odd, 1 .. 15");
+  if (gauss_ksize < 1 || gauss_ksize > 15 || !(gauss_ksize & 1))
+    return fail(HN_ERR_ARG, "gauss_ksize must be odd, 1 .. 15");
+  if (!(gauss_sigma >= 0.f) || !std::isfinite(gauss_sigma))
+    return fail(HN_ERR_ARG, "gauss_sigma must be finite and >= 0");
+  if (nms_thresh != nms_thresh) return fail(HN_ERR_ARG, "nms_thresh is NaN");
+  if ((d_kori == nullptr) != (d_ori_map == nullptr))
+    return fail(HN_ERR_ARG, "d_kori and d_ori_map must both be given or both NULL");
+  if (n_images == 0) return HN_OK;
+  if (!d_score || !d_kpts || !d_kscore || !d_kscale || !d_workspace)
+    return fail(HN_ERR_ARG, "NULL device pointer (d_scale_map, d_ori_map / d_kori, d_score_proc, d_topk_mask may be)");
+  if (reinterpret_cast<uintptr_t>(d_workspace) & 15) return fail(HN_ERR_ARG, "d_workspace must be 16-byte aligned");
+  const size_t need = hn_select_ws_bytes(n_images, height, width);
+  if (workspace_bytes < need)
+    return fail(HN_ERR_WORKSPACE, "workspace too small: need " + std::to_string(need) + " bytes");
+  // get_gauss_filter_weight (image_utils.py:277-295): the exponent in its fp32 operation order, the exponential as
+  // the fp64 one rounded to fp32 (what any libm reproduces); not normalised; sigma 0: a delta
+  float taps[225];
+  const int c = gauss_ksize / 2;
+  const float two_s2 = 2.0f * (gauss_sigma * gauss_sigma);
+  for (int y = 0; y < gauss_ksize; ++y)
+    for (int x = 0; x < gauss_ksize; ++x) {
+      const float fx = (float)(x - c), fy = (float)(y - c);
+      taps[y * gauss_ksize + x] = gauss_sigma == 0.f ? (x == c && y == c ? 1.f : 0.f)
+                                                     : (float)std::exp((double)-((fx * fx) / two_s2 + (fy * fy) / two_s2));
+    }
+  HnSelectArgs a{};
+  a.score = d_score;
+  a.B = n_images;
+  a.H = height;
+  a.W = width;
+  a.border = border;
+  a.nms_thresh = nms_thresh;
+  a.nms_ksize = nms_ksize;
+  a.topk = topk;
+  a.gauss_ksize = gauss_ksize;
+  a.taps = taps;
+  a.scale_map = d_scale_map;
+  a.scale_value = scale_value;
+  a.ori_map = d_ori_map;
+  a.kpts = d_kpts;
+  a.kscore = d_kscore;
+  a.kscale = d_kscale;
+  a.kori = d_kori;
+  a.score_proc = d_score_proc;
+  a.topk_mask = d_topk_mask;
+  a.ws = d_workspace;
+  HIPCHK(hn_launch_select(a, static_cast<hipStream_t>(hip_stream)));
+  return HN_OK;
+}
+
+// ---------------------------------------------------------------------------------------
 // train-mode stock HardNet (hn_train.hip)
 // ---------------------------------------------------------------------------------------
 extern "C" int hn_hardnet_train_workspace_bytes(int64_t batch, size_t* saved_bytes_out, size_t* scratch_bytes_out) {

@@ -226,6 +226,49 @@ hipError_t hn_launch_match_nn2(const float* q, int N, const float* db, int M, in
 // ori null: no rotation.  Reads nothing outside images whatever the keypoint data (B >= 1, H, W >= 2)
 hipError_t hn_launch_clip(const float* images, int64_t B, int H, int W, const int64_t* kpts, const float* scale,
                           const float* ori, const float* ratio, int64_t n, float* out, hipStream_t st);
+// FDLNet's NASNet detector (hn_det.hip): layout of the BN-folded device parameters (floats) and the launch
+namespace hndet {
+constexpr int kDetTile = 16;      // k_det_feat's output tile (one partial-statistics slot per tile)
+constexpr int kDetPostTile = 32;  // k_det_post's
+constexpr int kC0W = 0;           // features.0.weight [16][9]
+constexpr int kC0B = 144;         // features.0.bias [16]
+constexpr int kBlk = 160;         // two InvertedResidual blocks of kBlkSize floats, BN folded:
+constexpr int kBlkPw1W = 0;       //   1x1 [8 out][8 in]
+constexpr int kBlkPw1B = 64;
+constexpr int kBlkDwW = 72;       //   depthwise [8][9]
+constexpr int kBlkDwB = 144;
+constexpr int kBlkPw2W = 152;     //   1x1 [8 out][8 in]
+constexpr int kBlkPw2B = 216;
+constexpr int kBlkSize = 224;
+constexpr int kHeadW = kBlk + 2 * kBlkSize;  // conv.weight, conv_ori.weight: [3][16][9] (score, cos, sin)
+constexpr int kHeadB = kHeadW + 432;         // [3]
+constexpr int kInG = kHeadB + 3;             // insnorm.weight, insnorm_ori.weight [3]
+constexpr int kInB = kInG + 3;               // insnorm.bias, insnorm_ori.bias [3]
+constexpr int kFolded = kInB + 3;
+constexpr int kStateFloats = 160 + 2 * (64 + 32 + 72 + 32 + 64 + 32) + 145 + 2 + 290 + 4;  // RFDet.state_dict()
+}  // namespace hndet
+int64_t hn_det_parts(int H, int W);  // partial-statistics slots (k_det_feat workgroups) per image
+size_t hn_det_ws_bytes(int64_t B, int H, int W);
+hipError_t hn_launch_det(const float* params, float in_eps, const float* images, int64_t B, int H, int W, float* score,
+                         float* ori, void* ws, hipStream_t st);
+// keypoint selection (hn_select.hip); taps: the gauss_ksize^2 blur weights, row-major (host memory)
+struct HnSelectArgs {
+  const float* score;
+  int64_t B;
+  int H, W, border;
+  float nms_thresh;
+  int nms_ksize, topk, gauss_ksize;
+  const float* taps;
+  const float* scale_map;
+  float scale_value;
+  const float* ori_map;
+  int64_t* kpts;
+  float *kscore, *kscale, *kori, *score_proc;
+  uint8_t* topk_mask;
+  void* ws;
+};
+size_t hn_select_ws_bytes(int64_t B, int H, int W);
+hipError_t hn_launch_select(const HnSelectArgs& a, hipStream_t st);
 hipError_t hn_launch_loss(const float* pos, const float* rmin, const float* cmin, int n, float margin,
                           int type, float scale, float* min_neg, float* loss, hipStream_t st);
 

@@ -1,0 +1,296 @@
+"""FDLNet's keypoint detector and keypoint selection: the first two steps of ``Network.inference``
+(FDLNet-master/latency/NASNet/model/network.py:148-183)
+
+    detector -> process / topk_map -> clip_patch -> des(patches) -> NN / NNT / NNDR matching
+
+``RFDet`` is a drop-in for the NASNet variant's detector (model/det.py): the reference's constructor arguments,
+attributes and ``state_dict`` keys, so a reference checkpoint loads with ``strict=True``.  In eval mode on HIP fp32
+``[B,1,H,W]`` images with no autograd graph to record, ``forward`` runs ``hn_det_forward`` (two kernels, hn_det.hip)
+and ``process`` / ``detect`` run ``hn_select_keypoints`` (hn_select.hip).  Everywhere else -- CPU tensors, fp64,
+train mode, autograd -- the torch layers below run; they restate the reference formulas operation by operation and
+in fp64 are the ground truth of the tests.
+
+``select_keypoints_torch`` restates the selection with the C ABI's tie rule: both top-K steps order pixels by
+(value descending, flat index ascending) -- a stable descending sort -- where the reference leaves ties to
+``torch.sort``; a NaN score counts as 0.  Where no cut falls inside a group of equal values the two agree.
+
+``detect`` is image -> keypoints and ``detect_and_describe`` image -> descriptors (the reference ``inference``
+tuple), with no torch kernel and no host synchronisation between the image and the descriptors on the native path.
+"""
+from __future__ import annotations
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+BORDER = 8          # filter_border's radius (utils/image_utils.py:211)
+SOFT_NMS_KSIZE = 15  # soft_nms_3d's arguments in RFDet.forward (model/det.py:83)
+SOFT_NMS_STRENGTH = 7.0
+
+
+def channel_shuffle(x, groups):
+    """model/operations.py:437-447: new channel j * groups + g is old channel g * (C / groups) + j."""
+    b, c, h, w = x.shape
+    return x.view(b, groups, c // groups, h, w).transpose(1, 2).contiguous().view(b, c, h, w)
+
+
+class InvertedResidual(nn.Module):
+    """model/operations.py:449-511 with benchmodel 1, stride 1 (the only form the detector uses)."""
+
+    def __init__(self, inp, oup, stride, benchmodel):
+        super().__init__()
+        if benchmodel != 1 or stride != 1:
+            raise ValueError("the detector uses InvertedResidual(benchmodel=1, stride=1) only")
+        self.benchmodel, self.stride = benchmodel, stride
+        c = oup // 2
+        self.banch2 = nn.Sequential(
+            nn.Conv2d(c, c, 1, 1, 0, bias=False), nn.BatchNorm2d(c), nn.ReLU(inplace=True),
+            nn.Conv2d(c, c, 3, stride, 1, groups=c, bias=False), nn.BatchNorm2d(c),
+            nn.Conv2d(c, c, 1, 1, 0, bias=False), nn.BatchNorm2d(c), nn.ReLU(inplace=True))
+
+    def forward(self, x):
+        h = x.shape[1] // 2
+        return channel_shuffle(torch.cat((x[:, :h], self.banch2(x[:, h:])), 1), 2)
+
+
+def soft_nms_3d(scale_logits, ksize, com_strength):
+    """utils/image_utils.py:298-329 on [B,H,W,C] logits."""
+    x = scale_logits.permute(0, 3, 1, 2)
+    m = F.max_pool2d(x, kernel_size=ksize, padding=ksize // 2, stride=1).max(dim=1, keepdim=True)[0]
+    e = torch.exp(com_strength * (x - m))
+    s = F.conv2d(e, e.new_full([1, x.shape[1], ksize, ksize], 1.0), stride=1, padding=ksize // 2)
+    return (e / (s + 1e-8)).permute(0, 2, 3, 1)
+
+
+def soft_max_and_argmax_1d(input, scale_list, com_strength1, com_strength2):
+    """utils/image_utils.py:332-367 (dim -1, keepdim): (score_map, scale_map)."""
+    mx = input.max(dim=-1, keepdim=True)[0]
+    e1 = torch.exp(com_strength1 * (input - mx))
+    e2 = torch.exp(com_strength2 * (input - mx))
+    s1 = e1 / (e1.sum(dim=-1, keepdim=True) + 1e-8)
+    s2 = e2 / (e2.sum(dim=-1, keepdim=True) + 1e-8)
+    scale_list = scale_list.view(*([1] * (input.dim() - 1)), -1).to(device=input.device, dtype=input.dtype)
+    return (input * s1).sum(dim=-1, keepdim=True), (scale_list * s2).sum(dim=-1, keepdim=True)
+
+
+def gauss_filter_weight(ksize, sig):
+    """utils/image_utils.py:277-295 (fp32, not normalised; sigma 0 is a delta)."""
+    mu = ksize // 2
+    if sig == 0:
+        psf = torch.zeros((ksize, ksize)).float()
+        psf[mu, mu] = 1.0
+        return psf
+    sig = torch.tensor(sig).float()
+    x = torch.arange(ksize)[None, :].repeat(ksize, 1).float()
+    y = torch.arange(ksize)[:, None].repeat(1, ksize).float()
+    return torch.exp(-((x - mu) ** 2 / (2 * sig ** 2) + (y - mu) ** 2 / (2 * sig ** 2)))
+
+
+def gauss_taps_abi(ksize, sig):
+    """The blur weights as hn_select_keypoints computes them: the reference's fp32 exponent, the exponential
+    evaluated in fp64 and rounded to fp32 (equal to ``gauss_filter_weight`` up to the last bit of torch's fp32 exp)."""
+    import math
+    import numpy as np
+    mu, f = ksize // 2, np.float32
+    if sig == 0:
+        return gauss_filter_weight(ksize, 0)
+    two_s2 = f(2.0) * (f(sig) * f(sig))
+    rows = [[f(math.exp(float(-((f(x - mu) * f(x - mu)) / two_s2 + (f(y - mu) * f(y - mu)) / two_s2))))
+             for x in range(ksize)] for y in range(ksize)]
+    return torch.tensor(rows, dtype=torch.float32)
+
+
+def _blur_abi(g, psf):
+    """clamp(conv(g, psf), 0, 1) on fp32 [B,H,W] in hn_select_keypoints' arithmetic: taps in row-major order, each a
+    fused multiply-add -- emulated as the exact fp64 product plus the accumulator, rounded to fp32 (a true FMA but
+    for a double rounding of probability ~2^-29 per operation)."""
+    k = psf.shape[0]
+    pad = k // 2
+    b, h, w = g.shape
+    gp = F.pad(g, (pad, pad, pad, pad)).double()
+    acc = torch.zeros_like(g)
+    for ky in range(k):
+        for kx in range(k):
+            acc = (gp[:, ky:ky + h, kx:kx + w] * float(psf[ky, kx]) + acc.double()).float()
+    return acc.clamp(0.0, 1.0)
+
+
+def _nms_value(score, border, nms_thresh, nms_ksize):
+    """Steps 1-2 of the selection on [B,H,W]: f (border filtered, NaN as 0) and v = f keep."""
+    b, h, w = score.shape
+    s = torch.nan_to_num(score, nan=0.0) if torch.isnan(score).any() else score
+    f = torch.zeros_like(s)
+    f[:, border:h - border, border:w - border] = s[:, border:h - border, border:w - border]
+    t = torch.where(f < nms_thresh, torch.zeros_like(f), f)
+    pad = nms_ksize // 2
+    mx = F.max_pool2d(F.pad(t.unsqueeze(1), (pad, pad, pad, pad), value=0.0), nms_ksize, stride=1).squeeze(1)
+    v = f * (t >= mx).to(f.dtype)
+    return torch.where(v == 0, torch.zeros_like(v), v)  # -0 -> +0
+
+
+def _topk_mask(maps, k):
+    """[B,H,W] bool mask of the k largest per image, ties by lowest flat index (stable descending sort)."""
+    b = maps.shape[0]
+    flat = maps.reshape(b, -1)
+    idx = flat.sort(dim=-1, descending=True, stable=True)[1][:, :k]
+    mask = torch.zeros_like(flat, dtype=torch.bool)
+    mask.scatter_(1, idx, True)
+    return mask.view_as(maps)
+
+
+def select_keypoints_torch(score, border, nms_thresh, nms_ksize, topk, gauss_ksize, gauss_sigma, scale_map=None,
+                           scale_value=32.0, ori_map=None, abi_blur=False):
+    """The selection of ``hn_select_keypoints`` in torch, in the dtype of ``score`` [B,H,W]:
+    (kpts [B K,4] int64, kscore, kscale, kori or None, q [B,H,W], topk_mask [B,H,W] uint8, v [B,H,W]).
+    The blur is the reference's ``F.conv2d``; with ``abi_blur`` (fp32 only) it is the C ABI's, bit for bit (its
+    weights, tap order and fused multiply-adds), so that near-equal blurred values order as they do on the GPU."""
+    v = _nms_value(score, border, nms_thresh, nms_ksize)
+    mask = _topk_mask(v, topk)
+    g = v * mask.to(v.dtype)
+    if abi_blur:
+        q = _blur_abi(g, gauss_taps_abi(gauss_ksize, gauss_sigma))
+    else:
+        psf = gauss_filter_weight(gauss_ksize, gauss_sigma).to(device=score.device, dtype=score.dtype)
+        q = F.conv2d(g.unsqueeze(1), psf[None, None], stride=1, padding=gauss_ksize // 2).squeeze(1).clamp(0.0, 1.0)
+    top = _topk_mask(q, topk)
+    kp = top.nonzero()
+    kpts = torch.cat((kp, torch.zeros_like(kp[:, :1])), dim=1)
+    kscore = score[top]
+    kscale = scale_map[top] if scale_map is not None else score.new_full((kpts.shape[0],), scale_value)
+    kori = ori_map[top] if ori_map is not None else None
+    return kpts, kscore, kscale, kori, q, mask.to(torch.uint8), v
+
+
+class RFDet(nn.Module):
+    """model/det.py:14-166 (NASNet variant: one scale, 32)."""
+
+    def __init__(self, score_com_strength, scale_com_strength, nms_thresh, nms_ksize, topk, gauss_ksize, gauss_sigma):
+        super().__init__()
+        self.score_com_strength = score_com_strength
+        self.scale_com_strength = scale_com_strength
+        self.NMS_THRESH = nms_thresh
+        self.NMS_KSIZE = nms_ksize
+        self.TOPK = topk
+        self.GAUSSIAN_KSIZE = gauss_ksize
+        self.GAUSSIAN_SIGMA = gauss_sigma
+        self.features = nn.Sequential(nn.Conv2d(1, 16, kernel_size=3, stride=1, padding=1),
+                                      InvertedResidual(16, 16, 1, 1), InvertedResidual(16, 16, 1, 1))
+        self.conv = nn.Conv2d(in_channels=16, out_channels=1, kernel_size=3, stride=1, padding=1)
+        self.insnorm = nn.InstanceNorm2d(1, affine=True)
+        self.conv_ori = nn.Conv2d(in_channels=16, out_channels=2, kernel_size=3, stride=1, padding=1)
+        self.insnorm_ori = nn.InstanceNorm2d(2, affine=True)
+        self.scale_list = torch.tensor([32.0])
+        self._native = None  # (key, NativeDetector)
+
+    # ---- native path -------------------------------------------------------------------------------------------
+    def _native_ok(self, photos) -> bool:
+        return (not self.training and photos.is_cuda and photos.dtype == torch.float32 and photos.dim() == 4
+                and photos.shape[1] == 1 and photos.shape[0] > 0 and photos.shape[2] * photos.shape[3] >= 2
+                and self.conv.weight.device == photos.device
+                and not (torch.is_grad_enabled() and (photos.requires_grad
+                                                      or any(p.requires_grad for p in self.parameters()))))
+
+    def native_detector(self, device):
+        """The NativeDetector of the current weights on ``device`` (rebuilt when a tensor of the state changes)."""
+        from . import _native
+        key = (str(device),) + tuple((v.data_ptr(), v._version) for v in (*self.parameters(), *self.buffers()))
+        if self._native is None or self._native[0] != key:
+            self._native = (key, _native.NativeDetector(_native.state_dict_blob(self.state_dict()), device,
+                                                        bn_eps=self.features[1].banch2[1].eps, in_eps=self.insnorm.eps))
+        return self._native[1]
+
+    def forward_maps(self, photos):
+        """(score [B,H,W], ori [B,H,W,2]) of the native forward."""
+        return self.native_detector(photos.device).forward(photos.detach())
+
+    def _apply(self, fn, *a, **k):
+        self._native = None
+        return super()._apply(fn, *a, **k)
+
+    # ---- the reference's methods -------------------------------------------------------------------------------
+    def forward(self, photos):
+        if self._native_ok(photos):
+            score, ori = self.forward_maps(photos)
+            score = score.unsqueeze(-1)
+            return score, torch.full((), float(self.scale_list[0]), device=score.device).expand_as(score), ori
+        return self.forward_torch(photos)
+
+    def forward_torch(self, photos):
+        """The torch layers (model/det.py:57-94), whatever the device: the CPU / fp64 / training path."""
+        feature_map = self.features(photos)
+        feature_map_1 = F.leaky_relu(self.insnorm(self.conv(feature_map)))
+        ori_map = self.insnorm_ori(self.conv_ori(feature_map))
+        ori_map = (ori_map / torch.norm(ori_map, p=2, dim=1, keepdim=True)).permute(0, 2, 3, 1)
+        score_maps = feature_map_1.permute(0, 2, 3, 1)
+        scale_probs = soft_nms_3d(score_maps, ksize=SOFT_NMS_KSIZE, com_strength=SOFT_NMS_STRENGTH)
+        score_map, scale_map = soft_max_and_argmax_1d(scale_probs, self.scale_list, self.score_com_strength,
+                                                      self.scale_com_strength)
+        return score_map, scale_map, ori_map
+
+    def _select_args(self):
+        return (BORDER, float(self.NMS_THRESH), int(self.NMS_KSIZE), int(self.TOPK), int(self.GAUSSIAN_KSIZE),
+                float(self.GAUSSIAN_SIGMA))
+
+    def process(self, im1w_score):
+        """nms, top-K and Gaussian blur of a [B,H,W,1] score map (model/det.py:96-133):
+        (processed score, top-K mask uint8, NMS'd score), each [B,H,W,1]."""
+        s = im1w_score.squeeze(-1)
+        if (s.is_cuda and s.dtype == torch.float32 and s.shape[0] > 0
+                and not (torch.is_grad_enabled() and s.requires_grad)):
+            from . import _native
+            out = _native.select_keypoints(s.detach(), *self._select_args(), dense=True)
+            # the NMS'd score is no output of the C ABI (inference never reads it): a pad and a max-pool in torch
+            v = _nms_value(s.detach(), BORDER, float(self.NMS_THRESH), int(self.NMS_KSIZE))
+            return out["score_proc"].unsqueeze(-1), out["topk_mask"].unsqueeze(-1), v.unsqueeze(-1)
+        _, _, _, _, q, mask, v = select_keypoints_torch(s, *self._select_args())
+        return q.unsqueeze(-1), mask.unsqueeze(-1), v.unsqueeze(-1)
+
+    @staticmethod
+    def loss(left_score, im1gt_score, im1visible_mask):
+        l2_element_diff = (left_score - im1gt_score) ** 2
+        Nvi = torch.clamp(im1visible_mask.sum(dim=(3, 2, 1)), min=2.0)
+        return (torch.sum(l2_element_diff * im1visible_mask, dim=(3, 2, 1)) / (Nvi + 1e-8)).mean()
+
+    @staticmethod
+    def weights_init(m):
+        if isinstance(m, nn.Conv2d):
+            nn.init.xavier_uniform_(m.weight.data, gain=nn.init.calculate_gain("leaky_relu"))
+            try:
+                nn.init.xavier_uniform_(m.bias.data)
+            except Exception:
+                pass
+
+    @staticmethod
+    def convO_init(m):
+        if isinstance(m, nn.Conv2d):
+            nn.init.zeros_(m.weight.data)
+            try:
+                nn.init.ones_(m.bias.data)
+            except Exception:
+                pass
+
+
+def detect(det, im_data):
+    """Image -> keypoints (model/network.py:155-162, 181-182): ``(kpts [B K,4] int64 rows (b, y, x, 0) in raster
+    order per image, kscale [B K], kori [B K,2], kscore [B K], im_scale [B,H,W,1])``, K = ``det.TOPK``.  On the
+    native path this is ``hn_det_forward`` followed by ``hn_select_keypoints``, bit for bit."""
+    if det._native_ok(im_data):
+        from . import _native
+        score, ori = det.forward_maps(im_data)
+        scale_value = float(det.scale_list[0])
+        out = _native.select_keypoints(score, *det._select_args(), scale_value=scale_value, ori_map=ori)
+        im_scale = torch.full((), scale_value, device=score.device).expand(*score.shape, 1)
+        return out["kpts"], out["kscale"], out["kori"], out["kscore"], im_scale
+    im_rawsc, im_scale, im_orint = det(im_data)
+    kpts, kscore, kscale, kori, _, _, _ = select_keypoints_torch(
+        im_rawsc.squeeze(-1), *det._select_args(), scale_map=im_scale.squeeze(-1), ori_map=im_orint)
+    return kpts, kscale, kori, kscore, im_scale
+
+
+def detect_and_describe(det, des, im_data, im_info, im_raw):
+    """``Network.inference`` (model/network.py:148-183): ``(im_scale, kpts, im_des, scale, ori, score)`` --
+    ``detect`` chained into ``describe_keypoints``."""
+    from .patches import describe_keypoints
+    kpts, kscale, kori, kscore, im_scale = detect(det, im_data)
+    im_des = describe_keypoints(des, kpts, kscale, kori, im_info, im_raw)
+    return im_scale, kpts, im_des, kscale, kori, kscore

@@ -272,6 +272,72 @@ int hn_forward_kp(hn_model* m, const float* d_images, int64_t n_images, int32_t 
                   const int64_t* d_kpts, const float* d_scale, const float* d_ori, const float* d_ratio, int64_t n,
                   float* d_out, void* d_workspace, size_t workspace_bytes, void* hip_stream);
 
+/* FDLNet's keypoint detector, the first step of Network.inference (model/network.py:148-183): eval-mode
+ * RFDet.forward of the NASNet variant (FDLNet-master/latency/NASNet/model/det.py:57-94; single scale, pairs with
+ * HN_KIND_FDL_NASNET) for fp32 images, in fp32 FMA arithmetic, two kernel launches.
+ *   features.0 conv 1->16 3x3 (bias, no activation); two InvertedResidual(16,16,1,benchmodel=1) blocks
+ *   (model/operations.py:449-511: channels 0..7 pass, 8..15 through 1x1+BN+ReLU, depthwise 3x3+BN, 1x1+BN+ReLU,
+ *   concat, channel_shuffle(2): new channel 2j+g = old channel 8g+j); every 3x3 layer pads its own input with
+ *   zeros.  Score head: conv 16->1 3x3, InstanceNorm2d(1, affine) with THIS image's statistics (biased variance,
+ *   in_eps), leaky_relu(0.01), then soft_nms_3d(ksize 15, strength 7) (utils/image_utils.py:298-329):
+ *   m = 15x15 maximum (windows clipped at the image), e = exp(7 (s - m)), p = e / (15x15 box sum of e with zero
+ *   padding + 1e-8).  Orientation head: conv 16->2 3x3, InstanceNorm2d(2, affine), division by the pair's L2
+ *   norm (no epsilon, as the reference).  soft_max_and_argmax_1d over the one scale is the identity on p in fp32
+ *   and the scale map is the constant scale_list[0] = 32: neither is computed.
+ * host_params: every float tensor of RFDet.state_dict() in its order, num_batches_tracked left out --
+ *   features.0.{weight,bias}; for features.1 and features.2: banch2.0.weight, banch2.1.{weight,bias,running_mean,
+ *   running_var}, banch2.3.weight, banch2.4.{...}, banch2.5.weight, banch2.6.{...}; conv.{weight,bias};
+ *   insnorm.{weight,bias}; conv_ori.{weight,bias}; insnorm_ori.{weight,bias}: 40 tensors, hn_det_param_count
+ *   floats (1,193).  BatchNorm (eval mode, bn_eps) is folded into the weights at create time, in double.
+ * d_images [n_images,1,height,width] fp32 contiguous -> d_score [n_images,height,width] (the reference's
+ * im_rawsc), d_ori [n_images,height,width,2] (cos, sin; 8-byte aligned).  Workspace (16-byte aligned):
+ * hn_det_workspace_bytes = the three pre-norm maps plus 48 bytes per 16x16 tile; a short one is
+ * HN_ERR_WORKSPACE.  The InstanceNorm statistics are per-workgroup fp64 partial sums combined in fp64 in a fixed
+ * order (no float atomics): an image's maps are bit-identical call to call, alone or inside any batch.
+ * Caller's stream, no allocation or synchronisation inside (capturable); every argument check runs before the GPU
+ * is touched: n_images >= 0 (0 returns HN_OK), height, width >= 1 with height * width in 2 .. 2^31 - 1,
+ * n_images * ceil(height / 16) * ceil(width / 16) < 2^31. */
+typedef struct hn_detector hn_detector;
+int hn_det_param_count(size_t* n_out);
+int hn_det_create(const float* host_params, size_t n_params, float bn_eps, float in_eps, hn_detector** out);
+int hn_det_workspace_bytes(int64_t n_images, int32_t height, int32_t width, size_t* bytes_out);
+int hn_det_forward(hn_detector* d, const float* d_images, int64_t n_images, int32_t height, int32_t width,
+                   float* d_score, float* d_ori, void* d_workspace, size_t workspace_bytes, void* hip_stream);
+void hn_det_destroy(hn_detector* d);
+
+/* Keypoint selection, the step between the detector's score map and hn_clip_patch: RFDet.process followed by
+ * Network.inference's second topk_map, nonzero() and gathers (model/det.py:96-133, model/network.py:155-183,
+ * utils/image_utils.py:197-274) for any score map d_score [n_images,height,width] fp32, K = topk:
+ *   1. f = s inside the border, 0 within `border` pixels of an edge (filter_border; the reference's radius is 8);
+ *      a NaN score counts as 0.
+ *   2. t = f < nms_thresh ? 0 : f; keep where t >= the maximum of t over the nms_ksize x nms_ksize window, with 0
+ *      outside the image; v = f keep.
+ *   3. per image the K largest v form the mask; g = v mask.
+ *   4. q = clamp(conv(g, psf, zero padding gauss_ksize / 2), 0, 1), psf[y][x] = exp(-((x-c)^2 / (2 sigma^2) +
+ *      (y-c)^2 / (2 sigma^2))) in fp32, NOT normalised; sigma == 0 is a delta; taps summed in row-major order.
+ *   5. per image the K largest q are the keypoints (yes: the second top-K runs on the blurred map).
+ *   6. the keypoints leave in raster order per image, images in order, as nonzero() lists them:
+ *      d_kpts [n_images K, 4] int64 rows (b, y, x, 0); d_kscore [n_images K] = s at the keypoint (the raw score);
+ *      d_kscale [n_images K] from d_scale_map [n_images,height,width], or scale_value where the map is NULL;
+ *      d_kori [n_images K, 2] from d_ori_map [n_images,height,width,2] (both given or both NULL).
+ *      Optional dense outputs (process's own return values; NULL to skip): d_score_proc [n_images,height,width]
+ *      = q, d_topk_mask [n_images,height,width] uint8 = the mask of step 3.
+ * The one deliberate difference from the reference (next to hn_match_nn2's): both top-K steps order pixels by
+ * (value descending, flat index ascending), where the reference leaves ties to torch.sort.  So fewer than K
+ * positive pixels are filled up with the zeros of lowest index, and the result does not depend on the order in
+ * which workgroups finish.  The output count is exactly n_images K: nothing is read back, no allocation or
+ * synchronisation inside (capturable), no float atomics.  Workspace (16-byte aligned): hn_select_workspace_bytes
+ * = three fp32 maps; every byte of it is written before it is read.
+ * Every argument check runs before the GPU is touched: n_images >= 0 (0 returns HN_OK), 1 <= topk <= height *
+ * width < 2^31, border >= 0 with height, width > 2 border, nms_ksize and gauss_ksize odd in 1 .. 15,
+ * gauss_sigma finite and >= 0, nms_thresh not NaN, d_kori and d_ori_map both or neither; else HN_ERR_ARG. */
+int hn_select_workspace_bytes(int64_t n_images, int32_t height, int32_t width, int32_t topk, size_t* bytes_out);
+int hn_select_keypoints(const float* d_score, int64_t n_images, int32_t height, int32_t width, int32_t border,
+                        float nms_thresh, int32_t nms_ksize, int32_t topk, int32_t gauss_ksize, float gauss_sigma,
+                        const float* d_scale_map, float scale_value, const float* d_ori_map, int64_t* d_kpts,
+                        float* d_kscore, float* d_kscale, float* d_kori, float* d_score_proc, uint8_t* d_topk_mask,
+                        void* d_workspace, size_t workspace_bytes, void* hip_stream);
+
 /* Train-mode stock HardNet (the module of hardnet/HardNet.py:275-315 in
  * model.train() as the training loop :379-441 runs it through autograd).
  *  forward : input_norm (mean / std detached), 7 x [conv -> BatchNorm2d(affine=False) with the
