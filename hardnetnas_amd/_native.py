@@ -54,7 +54,8 @@ EXPORTED = ["hn_param_count", "hn_create", "hn_workspace_bytes", "hn_forward",
             "hn_hardnet_train_workspace_bytes", "hn_hardnet_train_forward", "hn_hardnet_train_backward",
             "hn_nas_train_tensor_count", "hn_nas_train_workspace_bytes", "hn_nas_train_forward",
             "hn_nas_train_backward", "hn_hardnet_loss_train_workspace_bytes", "hn_hardnet_loss_train_forward",
-            "hn_hardnet_loss_backward", "hn_fpr95_workspace_bytes",
+            "hn_hardnet_loss_backward", "hn_neimask_loss_workspace_bytes", "hn_neimask_loss_forward",
+            "hn_neimask_loss_backward", "hn_fpr95_workspace_bytes",
             "hn_fpr95", "hn_match_workspace_bytes", "hn_match_nn2", "hn_clip_patch", "hn_workspace_bytes_kp",
             "hn_forward_kp", "hn_det_param_count", "hn_det_create", "hn_det_workspace_bytes", "hn_det_forward",
             "hn_det_destroy", "hn_select_workspace_bytes", "hn_select_keypoints", "hn_preprocess", "hn_set_profiling",
@@ -105,6 +106,9 @@ def load_library():
         lib.hn_hardnet_loss_train_workspace_bytes.argtypes = [I64, ctypes.POINTER(S)]
         lib.hn_hardnet_loss_train_forward.argtypes = [P, P, I64, I32, I32, ctypes.c_float, I32, P, P, S, P]
         lib.hn_hardnet_loss_backward.argtypes = [P, P, I64, I32, I32, ctypes.c_float, I32, P, P, P, P, S, P]
+        lib.hn_neimask_loss_workspace_bytes.argtypes = [I64, ctypes.POINTER(S)]
+        lib.hn_neimask_loss_forward.argtypes = [P, P, P, P, I64, I32, ctypes.c_float, ctypes.c_float, P, P, P, P, S, P]
+        lib.hn_neimask_loss_backward.argtypes = [P, P, I64, I32, ctypes.c_float, P, P, P, P, S, P]
         lib.hn_fpr95_workspace_bytes.argtypes = [I64, ctypes.POINTER(S)]
         lib.hn_fpr95.argtypes = [P, P, P, I64, I32, P, P, P, S, P]
         lib.hn_match_workspace_bytes.argtypes = [I64, I64, ctypes.POINTER(S)]
@@ -137,7 +141,8 @@ def load_library():
                      "hn_hardnet_train_workspace_bytes", "hn_hardnet_train_forward",
                      "hn_hardnet_train_backward", "hn_nas_train_tensor_count", "hn_nas_train_workspace_bytes",
                      "hn_nas_train_forward", "hn_nas_train_backward", "hn_hardnet_loss_train_workspace_bytes",
-                     "hn_hardnet_loss_train_forward", "hn_hardnet_loss_backward", "hn_match_workspace_bytes",
+                     "hn_hardnet_loss_train_forward", "hn_hardnet_loss_backward", "hn_neimask_loss_workspace_bytes",
+                     "hn_neimask_loss_forward", "hn_neimask_loss_backward", "hn_match_workspace_bytes",
                      "hn_match_nn2", "hn_clip_patch", "hn_workspace_bytes_kp", "hn_forward_kp",
                      "hn_det_param_count", "hn_det_create", "hn_det_workspace_bytes", "hn_det_forward",
                      "hn_select_workspace_bytes", "hn_select_keypoints"):
@@ -463,6 +468,70 @@ class HardNetLossFunction(torch.autograd.Function):
                                                 lt, dl.data_ptr(), ga.data_ptr(), gp.data_ptr(), saved.data_ptr(),
                                                 saved.numel(), stream), "hn_hardnet_loss_backward")
         return ga, gp, None, None, None
+
+
+def _aligned16(x: torch.Tensor) -> torch.Tensor:
+    """A contiguous, detached x whose rows the C ABI can take (16-byte aligned: a contiguous view at an odd
+    storage offset is copied)."""
+    x = x.detach().contiguous()
+    return x if x.data_ptr() % 16 == 0 else x.clone()
+
+
+def neimask_loss_forward(anchor, positive, anchor_kp, positive_kp, margin: float = 1.0, C: float = 5.0):
+    """``hn_neimask_loss_forward`` on fp32 [N,128] descriptors and int64 [N,4] keypoints of one HIP device.
+    Returns (loss [], pos [N], min_neg [N], saved): ``saved`` is the uint8 workspace the backward reads --
+    row keys [N] u64 then column keys [N] u64 (value bits << 32 | argmin), each block 256-byte aligned
+    (``neimask_saved_argmins``)."""
+    lib = load_library()
+    a, p, ak, pk = (_aligned16(x) for x in (anchor, positive, anchor_kp, positive_kp))
+    b = a.shape[0]
+    n = ctypes.c_size_t()
+    _check(lib.hn_neimask_loss_workspace_bytes(b, ctypes.byref(n)), "hn_neimask_loss_workspace_bytes")
+    saved = torch.empty(n.value, device=a.device, dtype=torch.uint8)
+    loss = torch.empty((), device=a.device, dtype=torch.float32)
+    pos, mn = (torch.empty(b, device=a.device, dtype=torch.float32) for _ in range(2))
+    stream = torch.cuda.current_stream(a.device).cuda_stream
+    with torch.cuda.device(a.device):
+        _check(lib.hn_neimask_loss_forward(a.data_ptr(), p.data_ptr(), ak.data_ptr(), pk.data_ptr(), b, a.shape[1],
+                                           float(margin), float(C), loss.data_ptr(), pos.data_ptr(), mn.data_ptr(),
+                                           saved.data_ptr(), saved.numel(), stream), "hn_neimask_loss_forward")
+    return loss, pos, mn, saved
+
+
+def neimask_saved_argmins(saved: torch.Tensor, n: int):
+    """(row argmin [n], column argmin [n]) int64 out of a neighbour-mask loss workspace."""
+    blk = (8 * n + 255) // 256 * 256
+    keys = saved[:2 * blk].view(torch.int64)
+    return keys[:n] & 0xffffffff, keys[blk // 8:blk // 8 + n] & 0xffffffff
+
+
+class NeiMaskLossFunction(torch.autograd.Function):
+    """FDLNet's neighbour-mask descriptor loss (FDLNet-master/latency/NASNet/model/des.py:57-96) and its
+    backward on the fused kernels of hn_neimask.hip: no N x N matrix, the gradient routed to each row's positive
+    and its selected hardest negative as autograd routes it through the reference formulation.
+    anchor / positive: [N,128] fp32, anchor_kp / positive_kp: [N,4] int64 rows (b, y, x, 0), one HIP device."""
+
+    @staticmethod
+    def forward(ctx, anchor, positive, anchor_kp, positive_kp, margin, C):
+        a, p = _aligned16(anchor), _aligned16(positive)
+        loss, _, _, saved = neimask_loss_forward(a, p, anchor_kp, positive_kp, margin, C)
+        ctx.margin = float(margin)
+        ctx.save_for_backward(a, p, saved)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable  # the fused backward records no graph (no double backward)
+    def backward(ctx, dloss):
+        lib = load_library()
+        a, p, saved = ctx.saved_tensors
+        ga, gp = torch.empty_like(a), torch.empty_like(p)
+        dl = dloss.detach().to(device=a.device, dtype=torch.float32).contiguous().reshape(1)
+        stream = torch.cuda.current_stream(a.device).cuda_stream
+        with torch.cuda.device(a.device):
+            _check(lib.hn_neimask_loss_backward(a.data_ptr(), p.data_ptr(), a.shape[0], a.shape[1], ctx.margin,
+                                                dl.data_ptr(), ga.data_ptr(), gp.data_ptr(), saved.data_ptr(),
+                                                saved.numel(), stream), "hn_neimask_loss_backward")
+        return ga, gp, None, None, None, None
 
 
 def hardnet_loss(pos: torch.Tensor, row_min: torch.Tensor, col_min: Optional[torch.Tensor] = None,

@@ -1834,6 +1834,50 @@ extern "C" int hn_hardnet_loss_backward(const float* d_anchor, const float* d_po
   return HN_OK;
 }
 
+extern "C" int hn_neimask_loss_workspace_bytes(int64_t batch, size_t* bytes_out) {
+  if (!bytes_out || batch < 1 || batch > (1 << 22)) return fail(HN_ERR_ARG, "batch out of range");
+  *bytes_out = hn_neimask_saved_bytes((long)batch);
+  return HN_OK;
+}
+
+static int neimask_args(const float* a, const float* p, int64_t batch, int32_t dim, void* saved, size_t saved_bytes) {
+  if (!a || !p || !saved) return fail(HN_ERR_ARG, "NULL device pointer");
+  if (batch < 1 || batch > (1 << 22)) return fail(HN_ERR_ARG, "batch out of range");
+  if (dim != 128) return fail(HN_ERR_ARG, "dim must be 128");
+  if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(saved)) & 15)
+    return fail(HN_ERR_ARG, "device pointers must be 16-byte aligned");
+  if (saved_bytes < hn_neimask_saved_bytes((long)batch)) return fail(HN_ERR_WORKSPACE, "saved workspace too small");
+  return HN_OK;
+}
+
+extern "C" int hn_neimask_loss_forward(const float* d_anchor, const float* d_positive, const int64_t* d_anchor_kp,
+                                       const int64_t* d_positive_kp, int64_t batch, int32_t dim, float margin,
+                                       float coo_thresh, float* d_loss, float* d_pos, float* d_min_neg, void* d_saved,
+                                       size_t saved_bytes, void* hip_stream) {
+  if (int rc = neimask_args(d_anchor, d_positive, batch, dim, d_saved, saved_bytes)) return rc;
+  if (!d_anchor_kp || !d_positive_kp || !d_loss) return fail(HN_ERR_ARG, "NULL device pointer");
+  if ((reinterpret_cast<uintptr_t>(d_anchor_kp) | reinterpret_cast<uintptr_t>(d_positive_kp)) & 7)
+    return fail(HN_ERR_ARG, "keypoint pointers must be 8-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(d_loss) | reinterpret_cast<uintptr_t>(d_pos) | reinterpret_cast<uintptr_t>(d_min_neg)) & 3)
+    return fail(HN_ERR_ARG, "output pointers must be 4-byte aligned");
+  HIPCHK(hn_launch_neimask_fwd(d_anchor, d_positive, reinterpret_cast<const long long*>(d_anchor_kp),
+                               reinterpret_cast<const long long*>(d_positive_kp), (int)batch, margin, coo_thresh, d_loss,
+                               d_pos, d_min_neg, d_saved, static_cast<hipStream_t>(hip_stream)));
+  return HN_OK;
+}
+
+extern "C" int hn_neimask_loss_backward(const float* d_anchor, const float* d_positive, int64_t batch, int32_t dim,
+                                        float margin, const float* d_dloss, float* d_grad_anchor,
+                                        float* d_grad_positive, void* d_saved, size_t saved_bytes, void* hip_stream) {
+  if (int rc = neimask_args(d_anchor, d_positive, batch, dim, d_saved, saved_bytes)) return rc;
+  if (!d_dloss || !d_grad_anchor || !d_grad_positive) return fail(HN_ERR_ARG, "NULL device pointer");
+  if ((reinterpret_cast<uintptr_t>(d_grad_anchor) | reinterpret_cast<uintptr_t>(d_grad_positive)) & 7)
+    return fail(HN_ERR_ARG, "gradient pointers must be 8-byte aligned");
+  HIPCHK(hn_launch_neimask_bwd(d_anchor, d_positive, (int)batch, margin, d_dloss, d_grad_anchor, d_grad_positive,
+                               d_saved, static_cast<hipStream_t>(hip_stream)));
+  return HN_OK;
+}
+
 extern "C" int hn_pairdist_workspace_bytes(int64_t batch, size_t* bytes_out) {
   if (!bytes_out || batch < 0) return fail(HN_ERR_ARG, "bad argument");
   // column minima (padded to 64 entries) + the row kernel's workspace (hn_pairdist_rows_ws_bytes)

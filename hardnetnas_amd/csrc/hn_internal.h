@@ -380,3 +380,11 @@ hipError_t hn_launch_loss_train_fwd(const float* a, const float* p, int B, int s
                                     float* loss, void* saved, hipStream_t st);
 hipError_t hn_launch_loss_train_bwd(const float* a, const float* p, int B, int swap, float margin, int type,
                                     const float* dloss, float* ga, float* gp, void* saved, hipStream_t st);
+
+// FDLNet's neighbour-mask loss and its backward (hn_neimask.hip); akp / pkp: [B,4] int64 rows (b, y, x, 0)
+size_t hn_neimask_saved_bytes(long B);
+hipError_t hn_launch_neimask_fwd(const float* a, const float* p, const long long* akp, const long long* pkp, int B,
+                                 float margin, float coo_thresh, float* loss, float* pos_out, float* mn_out,
+                                 void* saved, hipStream_t st);
+hipError_t hn_launch_neimask_bwd(const float* a, const float* p, int B, float margin, const float* dloss, float* ga,
+                                 float* gp, void* saved, hipStream_t st);

@@ -24,19 +24,11 @@
 // scans all sources in order).
 #include "hn_common.h"
 #include "hn_internal.h"
+#include "hn_loss_gather.h"
 
 namespace {
 
-constexpr int D = 128;   // descriptor length
-constexpr int TM = 64;   // rows (anchors) per workgroup
-constexpr int TN = 64;   // columns (positives) per tile
-
-HN_DEV unsigned long long key_of(float v, int idx) {
-  return ((unsigned long long)__float_as_uint(v) << 32) | (unsigned)idx;
-}
-HN_DEV float key_val(unsigned long long k) { return __uint_as_float((unsigned)(k >> 32)); }
-HN_DEV int key_idx(unsigned long long k) { return (int)(unsigned)(k & 0xffffffffu); }
-HN_DEV unsigned long long umin64(unsigned long long x, unsigned long long y) { return x < y ? x : y; }
+constexpr int D = LT_D, TM = LT_TM, TN = LT_TN;
 
 __global__ __launch_bounds__(256) void k_lmin_init(unsigned long long* __restrict__ colbest, int B) {
   for (int i = blockIdx.x * 256 + threadIdx.x; i < B; i += gridDim.x * 256) colbest[i] = ~0ull;
@@ -83,43 +75,17 @@ __global__ __launch_bounds__(256) void k_lmin_tiles(const float* __restrict__ a,
   const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
   const int r0 = blockIdx.x * TM;
   // anchors -> As (k-major); rows past B are zero (their results are never stored)
-  for (int e = tid; e < TM * D / 4; e += 256) {
-    const int row = e % TM, k4 = e / TM;  // consecutive threads: consecutive rows (conflict-free LDS stores)
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (r0 + row < B) v = reinterpret_cast<const float4*>(a + (size_t)(r0 + row) * D)[k4];
-    float* as = reinterpret_cast<float*>(&As[0][0]);
-    as[(4 * k4 + 0) * TM + row] = v.x;
-    as[(4 * k4 + 1) * TM + row] = v.y;
-    as[(4 * k4 + 2) * TM + row] = v.z;
-    as[(4 * k4 + 3) * TM + row] = v.w;
-  }
+  lt_load_kmajor(reinterpret_cast<float*>(&As[0][0]), a, r0, B, tid);
   float asq[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) asq[r] = (r0 + 4 * ty + r < B) ? sq[r0 + 4 * ty + r] : 0.f;
   unsigned long long best[4] = {~0ull, ~0ull, ~0ull, ~0ull};
   for (int c0 = 0; c0 < B; c0 += TN) {
     __syncthreads();  // previous tile's readers are done with Ps / red
-    for (int e = tid; e < TN * D / 4; e += 256) {
-      const int col = e % TN, k4 = e / TN;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (c0 + col < B) v = reinterpret_cast<const float4*>(p + (size_t)(c0 + col) * D)[k4];
-      float* ps = reinterpret_cast<float*>(&Ps[0][0]);
-      ps[(4 * k4 + 0) * TN + col] = v.x;
-      ps[(4 * k4 + 1) * TN + col] = v.y;
-      ps[(4 * k4 + 2) * TN + col] = v.z;
-      ps[(4 * k4 + 3) * TN + col] = v.w;
-    }
+    lt_load_kmajor(reinterpret_cast<float*>(&Ps[0][0]), p, c0, B, tid);
     __syncthreads();
-    float acc[4][4] = {};
-#pragma unroll 4
-    for (int k = 0; k < D; ++k) {
-      const float4 av = As[k][ty], pv = Ps[k][tx];
-      const float ar[4] = {av.x, av.y, av.z, av.w}, pc[4] = {pv.x, pv.y, pv.z, pv.w};
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) acc[r][c] = fmaf(ar[r], pc[c], acc[r][c]);
-    }
+    float acc[4][4];
+    lt_tile_dots(As, Ps, ty, tx, acc);
     unsigned long long cb[4] = {~0ull, ~0ull, ~0ull, ~0ull};
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
@@ -211,19 +177,6 @@ __global__ __launch_bounds__(1024) void k_lmin_finish(const unsigned long long* 
   }
 }
 
-HN_DEV float dot128(const float* x, const float* y) {
-  const float4* a = reinterpret_cast<const float4*>(x);
-  const float4* b = reinterpret_cast<const float4*>(y);
-  float s = 0.f;
-  for (int k = 0; k < D / 4; ++k) {
-    const float4 u = a[k], v = b[k];
-    s = fmaf(u.x, v.x, s);
-    s = fmaf(u.y, v.y, s);
-    s = fmaf(u.z, v.z, s);
-    s = fmaf(u.w, v.w, s);
-  }
-  return s;
-}
 // 1 / (2 sqrt(u)) for entry (i, j): sqrt's backward factor
 HN_DEV float half_rsq(const float* a, const float* p, const float* sq, int B, int i, int j) {
   const float x = (sq[i] + sq[B + j]) - 2.0f * dot128(a + (size_t)i * D, p + (size_t)j * D);
@@ -262,107 +215,13 @@ __global__ __launch_bounds__(256) void k_lmin_bwd_src(const float* __restrict__ 
   idx[2 * i + 1] = c;
 }
 
-// Per-target source lists.  Target t < B is anchor t (sources k with a column negative c_k = t, coef
-// slot 2; only with anchor_swap), t >= B positive t - B (sources with a row negative r_k = t - B, slot 1).
-HN_DEV int src_target(const float* coef, const int* idx, int k, int slot, int B) {  // -1: no term
-  if (coef[3 * k + 1 + slot] == 0.f) return -1;
-  return slot ? idx[2 * k + 1] : B + idx[2 * k];
-}
-__global__ __launch_bounds__(256) void k_lmin_bwd_count(const float* __restrict__ coef, const int* __restrict__ idx,
-                                                        int B, int swap, int* __restrict__ cnt) {
-  for (int k = blockIdx.x * 256 + threadIdx.x; k < B; k += gridDim.x * 256)
-    for (int slot = 0; slot < 1 + swap; ++slot) {
-      const int tg = src_target(coef, idx, k, slot, B);
-      if (tg >= 0) atomicAdd(cnt + tg, 1);
-    }
-}
-// exclusive scan of cnt[n] -> off[n] in one workgroup (contiguous chunk per thread); fill[] := 0
-__global__ __launch_bounds__(1024) void k_lmin_bwd_scan(const int* __restrict__ cnt, int n, int* __restrict__ off,
-                                                        int* __restrict__ fill) {
-  __shared__ int tot[1024];
-  const int tid = threadIdx.x, per = (n + 1023) / 1024, b0 = min(n, tid * per), b1 = min(n, b0 + per);
-  int s = 0;
-  for (int i = b0; i < b1; ++i) s += cnt[i];
-  tot[tid] = s;
-  __syncthreads();
-  for (int o = 1; o < 1024; o <<= 1) {  // inclusive scan of the thread totals
-    const int v = tid >= o ? tot[tid - o] : 0;
-    __syncthreads();
-    tot[tid] += v;
-    __syncthreads();
-  }
-  int run = tot[tid] - s;
-  for (int i = b0; i < b1; ++i) {
-    off[i] = run;
-    run += cnt[i];
-    fill[i] = 0;
-  }
-}
-__global__ __launch_bounds__(256) void k_lmin_bwd_fill(const float* __restrict__ coef, const int* __restrict__ idx,
-                                                       int B, int swap, const int* __restrict__ off,
-                                                       int* __restrict__ fill, int* __restrict__ list) {
-  for (int k = blockIdx.x * 256 + threadIdx.x; k < B; k += gridDim.x * 256)
-    for (int slot = 0; slot < 1 + swap; ++slot) {
-      const int tg = src_target(coef, idx, k, slot, B);
-      if (tg >= 0) list[off[tg] + atomicAdd(fill + tg, 1)] = k;  // unordered; the gather orders it
-    }
-}
-
-// one wave per target row: t < B the anchor gradient of row t, else the positive gradient of row
-// t - B; each lane holds 2 of the 128 dims.  Terms: the target's own entries, then every source
-// whose selected negative lies in the target's row / column, in increasing source order.
-__global__ __launch_bounds__(256) void k_lmin_bwd_gather(const float* __restrict__ a, const float* __restrict__ p,
-                                                         int B, int swap, const float* __restrict__ coef,
-                                                         const int* __restrict__ idx, const int* __restrict__ cnt,
-                                                         const int* __restrict__ off, const int* __restrict__ list,
-                                                         float* __restrict__ ga, float* __restrict__ gp) {
-  const int t = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (t >= 2 * B) return;
-  const bool anc = t < B;
-  const int i = anc ? t : t - B;
-  const float2* A2 = reinterpret_cast<const float2*>(a);
-  const float2* P2 = reinterpret_cast<const float2*>(p);
-  // self = the target row's own vector, other(j) = the partner row on the other side
-  const float2 self = anc ? A2[(size_t)i * 64 + lane] : P2[(size_t)i * 64 + lane];
-  auto other = [&](int j) { return anc ? P2[(size_t)j * 64 + lane] : A2[(size_t)j * 64 + lane]; };
-  float2 acc = make_float2(0.f, 0.f);
-  auto add = [&](float w, const float2& o) {  // w (2 self - 2 other)
+// a selected entry's term: w d u / d self with u = |self|^2 + |other|^2 - 2 self.other + 1e-6
+struct L2Term {
+  static HN_DEV void add(float2& acc, float w, const float2& self, const float2& o) {
     acc.x = fmaf(w, 2.0f * self.x - 2.0f * o.x, acc.x);
     acc.y = fmaf(w, 2.0f * self.y - 2.0f * o.y, acc.y);
-  };
-  const float cpos = coef[3 * i];
-  if (cpos != 0.f) add(cpos, other(i));
-  // anchor row i: its own row negative (i, r_i); positive row i: its own column negative (c_i, i)
-  const float cown = coef[3 * i + (anc ? 1 : 2)];
-  if (cown != 0.f) add(cown, other(idx[2 * i + (anc ? 0 : 1)]));
-  // scattered terms: anchor i collects column negatives with c_k = i; positive j row negatives with r_k = j
-  const int slot = anc ? 1 : 0;
-  const int n = cnt[t];  // sources that selected an entry of this target (wave-uniform)
-  if (n > 0 && n <= 64) {
-    // the list in increasing source order: lane j holds source s_j, its rank = #{sources < s_j}
-    const int sj = lane < n ? list[off[t] + lane] : 0x7fffffff;
-    int rank = 0;
-    for (int o = 0; o < n; ++o) rank += __shfl(sj, o, 64) < sj ? 1 : 0;
-    for (int r = 0; r < n; ++r) {
-      const unsigned long long m = __ballot(lane < n && rank == r);
-      const int kk = __shfl(sj, __ffsll((unsigned long long)m) - 1, 64);
-      add(coef[3 * kk + 1 + slot], other(kk));
-    }
-  } else if (n > 64) {  // a heavily selected target: every source, in order
-    for (int k0 = 0; k0 < B; k0 += 64) {
-      const int k = k0 + lane;
-      const bool hit = k < B && idx[2 * k + slot] == i && coef[3 * k + 1 + slot] != 0.f;
-      unsigned long long m = __ballot(hit);
-      while (m) {
-        const int kk = k0 + __ffsll((unsigned long long)m) - 1;
-        m &= m - 1;
-        add(coef[3 * kk + 1 + slot], other(kk));
-      }
-    }
   }
-  float2* G = reinterpret_cast<float2*>(anc ? ga : gp);
-  G[(size_t)i * 64 + lane] = acc;
-}
+};
 
 }  // namespace
 
@@ -430,12 +289,5 @@ hipError_t hn_launch_loss_train_bwd(const float* a, const float* p, int B, int s
   const LossSaved s = loss_saved(saved, B);
   hipLaunchKernelGGL(k_lmin_bwd_src, dim3((B + 255) / 256), dim3(256), 0, st, a, p, s.sq, s.rowbest, s.colbest,
                      s.pos, s.posx, B, swap, margin, type, dloss, s.coef, s.idx);
-  const int g = std::min((B + 255) / 256, 2048);
-  if (hipError_t e = hipMemsetAsync(s.cnt, 0, sizeof(int) * 2 * (size_t)B, st)) return e;
-  hipLaunchKernelGGL(k_lmin_bwd_count, dim3(g), dim3(256), 0, st, s.coef, s.idx, B, swap, s.cnt);
-  hipLaunchKernelGGL(k_lmin_bwd_scan, dim3(1), dim3(1024), 0, st, s.cnt, 2 * B, s.off, s.fill);
-  hipLaunchKernelGGL(k_lmin_bwd_fill, dim3(g), dim3(256), 0, st, s.coef, s.idx, B, swap, s.off, s.fill, s.list);
-  hipLaunchKernelGGL(k_lmin_bwd_gather, dim3((2 * B + 3) / 4), dim3(256), 0, st, a, p, B, swap, s.coef, s.idx, s.cnt,
-                     s.off, s.list, ga, gp);
-  return hipGetLastError();
+  return lmin_bwd_gather_launch<L2Term>(a, p, B, swap, s.coef, s.idx, s.cnt, s.off, s.fill, s.list, ga, gp, st);
 }

@@ -7,12 +7,17 @@ autograd formulation below (the B x B matrix materialised, as in the reference) 
 tensors, the 'average' and 'random' reductions and ``fused=False``.  For inference-time mining at
 large B (65,536 pairs) ``hardnetnas_amd._native.pairdist_rows`` / ``hardnet_loss`` and
 ``hardnetnas_amd.distributed.sharded_hardnet_loss`` run the bf16x3 MFMA pair kernel (forward only).
+
+``loss_neimask`` is FDLNet's descriptor training loss (FDLNet-master/latency/NASNet/model/des.py:57-96): another
+distance (``matching.distance_matrix_vector``), two keypoint-neighbourhood masks in place of the < 0.008 rule,
+anchor swap always on; on HIP fp32 [N,128] descriptors it runs the fused kernels of hn_neimask.hip.
+``pair_distance_loss`` is the mean positive distance ``Network.criterion`` reports beside it (network.py:300-301).
 """
 from __future__ import annotations
 
 import torch
 
-__all__ = ["distance_matrix_vector", "loss_HardNet", "SupernetLoss"]
+__all__ = ["distance_matrix_vector", "loss_HardNet", "SupernetLoss", "loss_neimask", "pair_distance_loss"]
 
 
 def distance_matrix_vector(anchor: torch.Tensor, positive: torch.Tensor) -> torch.Tensor:
@@ -92,3 +97,55 @@ class SupernetLoss(torch.nn.Module):
                           * 0.2, 0)
         loss = self.alpha * (ce + lat)
         return loss, ce, lat
+
+
+def _keypoint_distances(kp: torch.Tensor) -> torch.Tensor:
+    """pairwise_distances(x, x) (utils/math_utils.py:22-40) on the (y, x) columns of [N,4] keypoint rows cast to
+    fp32, as des.py:76-84 calls it: sqrt(max(|x_i|^2 + |x_j|^2 - 2 x_i.x_j, 1e-8))."""
+    x = kp[:, 1:3].to(torch.float)
+    n = (x ** 2).sum(1)
+    return torch.sqrt((n.view(-1, 1) + n.view(1, -1) - 2.0 * torch.mm(x, x.t())).clamp(min=1e-8))
+
+
+def neimask_masked_distances(anchor, positive, anchor_kp, positive_kp, C: float):
+    """(D, dn) of des.py:68-87: the [N,N] descriptor distances and the same with 10 added on the diagonal and
+    wherever the anchor keypoints, and again wherever the positive keypoints, lie closer than C."""
+    from .matching import distance_matrix_vector as unit_distances
+    d = unit_distances(anchor, positive)
+    dn = d + torch.eye(d.size(1), device=d.device) * 10  # (an fp32 eye, as the reference builds it)
+    dn = dn + _keypoint_distances(anchor_kp).lt(C).to(torch.float) * 10
+    dn = dn + _keypoint_distances(positive_kp).lt(C).to(torch.float) * 10
+    return d, dn
+
+
+def loss_neimask(anchor: torch.Tensor, positive: torch.Tensor, anchor_kp: torch.Tensor, positive_kp: torch.Tensor,
+                 margin: float = 1.0, C: float = 5.0, fused: bool = True) -> torch.Tensor:
+    """FDLNet's neighbour-mask hardest-in-batch margin loss (``HardNetNeiMask.loss``, des.py:57-96):
+    mean_i max(margin + D_ii - min(min_j dn_ij, min_k dn_ki), 0).  The keypoints are [N,4] rows (b, y, x, 0); the
+    image index is not used, as in the reference; C = 0 gives the plain hardest-in-batch loss.
+
+    fp32 [N,128] descriptors with int64 [N,4] keypoints on one HIP device run the fused kernels
+    (``_native.NeiMaskLossFunction``: forward and backward, no N x N matrix, ties to the lowest index); CPU / fp64
+    tensors, other widths or dtypes and ``fused=False`` run the reference's formulation here."""
+    if anchor.size() != positive.size() or anchor.dim() != 2:
+        raise ValueError("anchor and positive must be 2-D tensors of the same shape")
+    for kp in (anchor_kp, positive_kp):
+        if kp.dim() != 2 or kp.size(0) != anchor.size(0) or kp.size(1) < 3:
+            raise ValueError("anchor_kp and positive_kp must be [N,4] keypoint rows (b, y, x, 0), one per descriptor")
+    if (fused and anchor.is_cuda and anchor.shape[1] == 128 and anchor.shape[0] >= 1
+            and anchor.dtype == torch.float32 and positive.dtype == torch.float32
+            and all(kp.dtype == torch.int64 and kp.shape[1] == 4 for kp in (anchor_kp, positive_kp))
+            and all(t.device == anchor.device for t in (positive, anchor_kp, positive_kp))):
+        from . import _native
+        return _native.NeiMaskLossFunction.apply(anchor, positive, anchor_kp, positive_kp, margin, C)
+    d, dn = neimask_masked_distances(anchor, positive, anchor_kp, positive_kp, C)
+    pos = d.diag()
+    min_neg = torch.min(dn.min(dim=1)[0], dn.min(dim=0)[0])
+    return torch.clamp(margin + pos - min_neg, min=0.0).mean()
+
+
+def pair_distance_loss(anchor: torch.Tensor, positive: torch.Tensor) -> torch.Tensor:
+    """``distance_matrix_vector(a, p).diag().mean()`` (network.py:300-301) row by row, without the matrix."""
+    if anchor.size() != positive.size() or anchor.dim() != 2:
+        raise ValueError("anchor and positive must be 2-D tensors of the same shape")
+    return (2 - 2 * (anchor * positive).sum(1)).clamp(min=1e-8, max=4.0).sqrt().mean()

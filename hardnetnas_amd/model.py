@@ -335,8 +335,8 @@ class HardNetNeiMask(_NativeMixin, nn.Module):
     ``variant="NASNet"`` = FDLNet-master/latency/NASNet/model/des.py:8-55,
     ``variant="NASNet_0.1"`` = latency/NASNet_0.1/model/des.py:10-55.  Same ``.features``
     indices / state_dict keys as the reference; input_norm eps 1e-8 (des.py:40-47); L2 by
-    ``torch.norm`` without eps (des.py:49-53).  The neighbour-mask training loss is not
-    part of the descriptor forward and is not restated here."""
+    ``torch.norm`` without eps (des.py:49-53).  ``loss`` is the neighbour-mask training loss
+    (des.py:57-96) with the reference's signature: ``losses.loss_neimask`` with this module's MARGIN and C."""
 
     def __init__(self, MARGIN: float = 1.0, C: float = 1.0, variant: str = "NASNet",
                  strict: bool = False):
@@ -377,6 +377,12 @@ class HardNetNeiMask(_NativeMixin, nn.Module):
         x_features = self.features(self.input_norm(input))
         x = x_features.view(x_features.size(0), -1)
         return x / torch.norm(x, p=2, dim=-1, keepdim=True)
+
+    def loss(self, anchor, positive, anchor_kp, positive_kp):
+        """The hard loss ``Network.criterion`` takes from its descriptor (network.py:307-308): fused kernels on
+        HIP fp32 descriptors, the reference's formulation elsewhere (``losses.loss_neimask``)."""
+        from .losses import loss_neimask
+        return loss_neimask(anchor, positive, anchor_kp, positive_kp, margin=self.MARGIN, C=self.C)
 
 
 class HardNetNAS(_NativeMixin, nn.Module):

@@ -170,6 +170,32 @@ int hn_hardnet_loss_backward(const float* d_anchor, const float* d_positive, int
                              float* d_grad_anchor, float* d_grad_positive, void* d_saved, size_t saved_bytes,
                              void* hip_stream);
 
+/* FDLNet's neighbour-mask descriptor loss (FDLNet-master/latency/NASNet/model/des.py:57-96, the hard loss of
+ * model/network.py:307-309) and its backward, without an N x N matrix:
+ *   D_ij  = sqrt(min(max(2 - 2 a_i.p_j, 1e-8), 4))  (exact fp32 dot products; rows need not be unit vectors)
+ *   dn_ij = ((D_ij + 10 [i = j]) + 10 [kd(anchor_kp_i, anchor_kp_j) < C]) + 10 [kd(positive_kp_i, positive_kp_j) < C]
+ *   loss  = mean_i max(margin + D_ii - min(min_j dn_ij, min_k dn_ki), 0)
+ * kd = sqrt(max(squared distance of the (y, x) columns, 1e-8)); d_anchor_kp / d_positive_kp: [batch,4] int64
+ * rows (b, y, x, 0), b not used (as in the reference).  The squared distance is taken from the integer
+ * differences: the reference's value for coordinates below 2,048; coordinates saturate at +-(2^30 - 1).  Any
+ * keypoint value is safe: keypoints never index memory.
+ *   forward : *d_loss; d_pos / d_min_neg ([batch], each may be NULL) receive D_ii and the selected minimum;
+ *             the minima and their argmins (the lowest index on a tie) are kept in d_saved;
+ *   backward: d_dloss (one float on the device) -> d_grad_anchor, d_grad_positive [batch,128] (overwritten),
+ *             as autograd differentiates the reference formulation: one argmin per minimum, halves on an exact
+ *             row / column tie, nothing through an active clamp.  Deterministic, bit-identical run to run.
+ * d_saved (hn_neimask_loss_workspace_bytes) is written by the forward and read by the backward with the same
+ * descriptors and margin; 1 <= batch <= 2^22; dim must be 128.  Non-finite descriptors give an unspecified
+ * loss and no out-of-bounds access. */
+int hn_neimask_loss_workspace_bytes(int64_t batch, size_t* bytes_out);
+int hn_neimask_loss_forward(const float* d_anchor, const float* d_positive, const int64_t* d_anchor_kp,
+                            const int64_t* d_positive_kp, int64_t batch, int32_t dim, float margin, float coo_thresh,
+                            float* d_loss, float* d_pos, float* d_min_neg, void* d_saved, size_t saved_bytes,
+                            void* hip_stream);
+int hn_neimask_loss_backward(const float* d_anchor, const float* d_positive, int64_t batch, int32_t dim, float margin,
+                             const float* d_dloss, float* d_grad_anchor, float* d_grad_positive, void* d_saved,
+                             size_t saved_bytes, void* hip_stream);
+
 /* FPR at 95 % recall of an evaluation batch of descriptor pairs (hardnet/HardNet.py:450-472
  * + hardnet/EvalMetrics.py:6-19): per-pair L2 distance, scores -> distances transform, sort,
  * first index reaching 95 % recall, FP / (FP + TN).
