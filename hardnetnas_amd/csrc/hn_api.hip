@@ -8,6 +8,7 @@
 #include "hn_internal.h"
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -45,6 +46,7 @@ void hn_read_knobs(HnKnobs* k) {
   k->front_xch3 = env_int("HN_FRONT_XCH3", 0) != 0;
   k->no_mpfront = env_int("HN_NO_MPFRONT", 0) != 0;
   k->pipeline = env_int("HN_PIPELINE", 0) != 0;
+  k->dyn_tiles = env_int("HN_STATIC_TILES", 0) != 0 ? 0 : env_int("HN_DYN_TILES", 3) & (kTilesConv3 | kTilesConv5);
 
   k->train_splitk = std::max(32, env_int("HN_TRAIN_SPLITK", 1024)) / 32 * 32;
   k->train_f32 = env_int("HN_TRAIN_F32", 17) & 255;
@@ -67,6 +69,15 @@ const HnKnobs& hn_knobs() {
   static HnKnobs process;
   std::call_once(once, [] { hn_read_knobs(&process); });
   return process;
+}
+
+// the calling forward's block of tile counters (TileScope, below hn_model) and the launches it has handed out
+static thread_local unsigned* tl_tile_block = nullptr;
+static thread_local unsigned tl_tile_launch = 0;
+
+unsigned* hn_tile_counters(int kernel) {
+  if (!tl_tile_block || !(hn_knobs().dyn_tiles & kernel)) return nullptr;
+  return tl_tile_block + 2 * (tl_tile_launch++ % kTileLaunches);
 }
 
 namespace {
@@ -269,6 +280,10 @@ struct hn_model {
   hipStream_t st2 = nullptr;
   hipEvent_t ev_fork = nullptr, ev_ready[2] = {nullptr, nullptr}, ev_free[2] = {nullptr, nullptr};
   std::mutex pipe_mu;
+  // work-tile counters of the claiming kernels (hn_tiles.h; hardnet_mi355x.h states what the ring bounds):
+  // HN_TILE_RING + HN_TILE_CAPTURES blocks of kTileLaunches (ticket, checked-out) pairs, all zero between launches
+  unsigned* tile_ctrs = nullptr;
+  std::atomic<unsigned> tile_next{0}, tile_captures{0};
 
   template <class T>
   int upload(const std::vector<T>& v, T** out) {
@@ -287,6 +302,39 @@ struct hn_model {
     if (st2) (void)hipStreamDestroy(st2);
   }
 };
+
+namespace {
+// One forward call's block of tile counters, current on the calling thread for the call: the ring's next block,
+// or -- while `st` is being captured -- one of the blocks set aside for graphs (none left: static tiling)
+struct TileScope {
+  unsigned* prev_block;
+  unsigned prev_launch;
+  TileScope(hn_model* m, hipStream_t st) : prev_block(tl_tile_block), prev_launch(tl_tile_launch) {
+    tl_tile_block = nullptr;
+    tl_tile_launch = 0;
+    if (!m->tile_ctrs || !m->knobs.dyn_tiles) return;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess) {
+      (void)hipGetLastError();
+      cs = hipStreamCaptureStatusNone;
+    }
+    unsigned b;
+    if (cs != hipStreamCaptureStatusNone) {
+      if (m->tile_captures.load() >= HN_TILE_CAPTURES) return;
+      b = m->tile_captures.fetch_add(1);
+      if (b >= HN_TILE_CAPTURES) return;
+      b += HN_TILE_RING;
+    } else {
+      b = m->tile_next.fetch_add(1) % HN_TILE_RING;
+    }
+    tl_tile_block = m->tile_ctrs + (size_t)b * 2 * kTileLaunches;
+  }
+  ~TileScope() {
+    tl_tile_block = prev_block;
+    tl_tile_launch = prev_launch;
+  }
+};
+}  // namespace
 
 // ---------------------------------------------------------------------------------------
 // parameter accounting
@@ -959,6 +1007,21 @@ extern "C" int hn_create(const hn_arch_desc* desc, const float* host_params, siz
     delete m;
     return rc;
   }
+  if (desc->kind == HN_KIND_HARDNET && m->knobs.dyn_tiles) {
+    // the tile counters, zeroed once (the claiming kernels leave them at zero); a failed allocation is not an
+    // error: the forward then tiles statically
+    const size_t bytes = (size_t)(HN_TILE_RING + HN_TILE_CAPTURES) * kTileLaunches * 2 * sizeof(unsigned);
+    void* p = nullptr;
+    if (hipMalloc(&p, bytes) == hipSuccess) {
+      if (hipMemset(p, 0, bytes) == hipSuccess && hipDeviceSynchronize() == hipSuccess) {
+        m->allocs.push_back(p);
+        m->tile_ctrs = static_cast<unsigned*>(p);
+      } else {
+        (void)hipFree(p);
+      }
+    }
+    if (!m->tile_ctrs) (void)hipGetLastError();
+  }
   *out = m;
   return HN_OK;
 }
@@ -1290,6 +1353,7 @@ extern "C" int hn_forward(hn_model* m, const float* d_in, int64_t batch, float* 
     return fail(HN_ERR_WORKSPACE, "workspace too small: need " + std::to_string(need) + " bytes");
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
   KnobScope knobs(&m->knobs);
+  TileScope tiles(m, st);
   if (hardnet_pipelined(m, batch)) return forward_hardnet_pipe(m, d_in, batch, d_out, static_cast<float*>(d_workspace), st);
   for (int64_t off = 0; off < batch; off += m->chunk) {
     const int P = (int)std::min<int64_t>(m->chunk, batch - off);
@@ -1352,6 +1416,7 @@ extern "C" int hn_forward_u8(hn_model* m, const uint8_t* d_in, int64_t batch, in
     return fail(HN_ERR_WORKSPACE, "workspace too small: need " + std::to_string(need) + " bytes");
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
   KnobScope knobs(&m->knobs);
+  TileScope tiles(m, st);
   const bool fused = u8_fused(m, resize);
   const size_t inb = (size_t)in_hw * in_hw;
   float* ws = static_cast<float*>(d_workspace);
@@ -1428,6 +1493,7 @@ extern "C" int hn_forward_kp(hn_model* m, const float* d_images, int64_t n_image
     return fail(HN_ERR_WORKSPACE, "workspace too small: need " + std::to_string(need) + " bytes");
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
   KnobScope knobs(&m->knobs);
+  TileScope tiles(m, st);
   float* ws = static_cast<float*>(d_workspace);
   hn_workspace_bytes(m, n, &base);
   float* patches = reinterpret_cast<float*>(static_cast<char*>(d_workspace) + base);

@@ -794,6 +794,14 @@ __global__ __launch_bounds__((WM * WN + 4) * 64) void k_conv_ws(
                             : (rb < ntiles ? (ntiles - 1 - rb) / nwg + 1 : 0);
   const int NS = my_tiles * C::NCC;
   if (NS == 0) return;
+  // ABL 64 (conv4 of a full chunk only; right results): lane 0 of wave 0 stamps the workgroup's start and end in
+  // the 100 MHz clock, past the chunk's workspace (in = a3 at its start, 40,960 floats per patch) behind k_c12s's
+  // 2 MiB and conv3's stamps (tools/tail_timeline.py)
+  long long* const stamps = reinterpret_cast<long long*>(const_cast<float*>(in) + (size_t)P * 40960 + (2 << 20) / 4) +
+                            1024 + 2 * blockIdx.x;
+  if constexpr ((ABL & 64) != 0) {
+    if (tid == 0) stamps[0] = (long long)__builtin_amdgcn_s_memrealtime();
+  }
   char* const buf0 = smem;
   char* const buf1 = smem + C::BUF;
   // PST staging slot of output pixel m of the tile whose last stage read buffer `b`
@@ -1204,6 +1212,9 @@ __global__ __launch_bounds__((WM * WN + 4) * 64) void k_conv_ws(
     }
   }
   if constexpr (PST) __builtin_amdgcn_s_barrier();  // B_y of the last tile
+  if constexpr ((ABL & 64) != 0) {
+    if (tid == 0) stamps[1] = (long long)__builtin_amdgcn_s_memrealtime();
+  }
 }
 
 // ------------------------------------------------------------------------------------
@@ -1946,6 +1957,8 @@ constexpr HnConvRow kConvRows[] = {
     {3, 4, row<3, Ws<64, 64, 16, 1, 1, 16, 2, 2, false, 40, 80, false, false>>},
     {4, 4, row<4, Ws<64, 128, 16, 2, 1, 8, 1, 4, false, 40, 80, false, false>>},
     {5, 4, row<5, Ws<128, 128, 8, 1, 2, 8, 1, 4, false, 40, 80, false, false>>},
+    // r: conv4's default (i) with start / end stamps per workgroup (ABL 64; right results, full chunks only)
+    {4, 27, row<4, Ws<64, 128, 16, 2, 2, 8, 2, 2, false, 64, 64, false, true>>},
 #endif
 };
 static_assert(hn_rows_unique(kConvRows), "one build per (layer, HN_VARIANT digit)");

@@ -33,6 +33,9 @@ struct HnKnobs {
   bool pipeline = false;       // HN_PIPELINE=1: HardNet batches of several chunks overlap chunk k + 1's k_c12s (second
                                // stream) with chunk k's conv3 .. head (opt-in: measured within noise)
   bool irf3 = false;           // HN_IRF3 (HN_EXPERIMENTS only): k_irf3 for layers 3 -> 4 -> 5 (measured slower)
+  int dyn_tiles = 3;           // HN_DYN_TILES: the persistent kernels that claim their work tiles (hn_tiles.h;
+                               // bits kTilesConv3 / kTilesConv5); HN_STATIC_TILES=1: none -- the static
+                               // assignment rb + k nwg, bit-identical results (the A/B arm and the oracle)
   int train_splitk = 1024;     // HN_TRAIN_SPLITK: K per split-K slice of the train GEMMs
   int train_f32 = 17;          // HN_TRAIN_F32: bit 0 train forward convs, bit 1 stride-1 dgrads as f32-MFMA
                                // GEMMs (else the bf16x3 conv kernels); 1 = every product f32; default 17 =
@@ -54,6 +57,16 @@ struct HnKnobs {
 };
 void hn_read_knobs(HnKnobs* k);
 const HnKnobs& hn_knobs();
+
+// Dynamic tile claiming (hn_tiles.h).  A forward call of a HardNet model takes one block of the model's counter
+// ring (hardnet_mi355x.h: HN_TILE_RING) and makes it current on the calling thread; each launch of a claiming kernel
+// inside the call gets the block's next (ticket, checked-out) counter pair, kTileLaunches pairs per block in
+// rotation -- launches that far apart are in stream order.  The counters are zero between launches (the kernels
+// reset them), so no call adds a stream operation.  Null -- no model in scope, HN_STATIC_TILES, `kernel` not in
+// HN_DYN_TILES, or the counters' allocation failed -- selects the static kernel.
+constexpr int kTilesConv3 = 1, kTilesConv5 = 2;  // HN_DYN_TILES bits
+constexpr int kTileLaunches = 32;
+unsigned* hn_tile_counters(int kernel);
 
 // Resident workgroups of `fn` on the current device at `nthreads` threads and `lds` bytes of
 // dynamic LDS (also raises the function's dynamic-LDS limit to `lds` on that device).  Cached

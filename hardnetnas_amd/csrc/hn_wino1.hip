@@ -24,6 +24,7 @@
 // bank-conflict free (tests/test_lds_banks.py).
 #include "hn_common.h"
 #include "hn_internal.h"
+#include "hn_tiles.h"
 
 namespace {
 
@@ -53,7 +54,8 @@ struct W1Cfg {
   static constexpr int SCR_OFF = 2 * BUF;
   static constexpr int SCR = CST ? 32 * SROW * 4 : 0;   // CST: one 32-pixel x 32-channel tile per MFMA wave
   static constexpr int BIAS_OFF = SCR_OFF + NWC * SCR;
-  static constexpr int SMEM = BIAS_OFF + COUT * 4;
+  static constexpr int TQ_OFF = BIAS_OFF + COUT * 4;  // DYN: the claimed tiles' ring (hn_tiles.h)
+  static constexpr int SMEM = TQ_OFF + hn_tiles::kSlots * 4;
   static constexpr int NKS = 24;  // K-steps per stage: 4 xi x 3 ky x 2 halves of 16 channels
   static constexpr unsigned CHUNK_BYTES = NKS * NTOT * 2 * 64 * 16;
   static_assert(SMEM <= 160 * 1024, "LDS");
@@ -87,12 +89,19 @@ constexpr int w1_fold_valu(bool first, int kx, int g) {
 
 // ABL (timing-only ablation builds, HN_EXPERIMENTS library only; wrong results): bit 0 idle producers
 // (barriers only), bit 1 no MFMAs (operands still loaded), bit 2 no weight loads (K-step 0's fragments
-// reused), bit 3 no epilogue stores, bit 4 idle MFMA waves, bit 5 no weight loads after the prologue
-template <int CIN, int COUT, int H, int NP, int WM, int WN, bool CST, int WD = 3, int ABL = 0>
+// reused), bit 3 no epilogue stores, bit 4 idle MFMA waves, bit 5 no weight loads after the prologue; bit 8 (right
+// results): lane 0 of wave 0 stamps the workgroup's start and end (100 MHz clock) into stamps[2 blockIdx.x + 0 / 1]
+// DYN: the workgroup's tiles past its first two are claimed from tile_ctr (hn_tiles.h) instead of rb + k nwg; the
+// producers' lane 0 claims.  The launch's grid never exceeds the tile count (every workgroup checks out).
+template <int CIN, int COUT, int H, int NP, int WM, int WN, bool CST, int WD = 3, int ABL = 0, bool DYN = false>
 __global__ __launch_bounds__((WM * WN + 4) * 64) void k_conv_w1(const float* __restrict__ in, float* __restrict__ out,
                                                                 const uint4* __restrict__ wp,
-                                                                const float* __restrict__ bias, int P) {
+                                                                const float* __restrict__ bias, int P,
+                                                                unsigned* __restrict__ tile_ctr,
+                                                                long long* __restrict__ stamps) {
   using C = W1Cfg<CIN, COUT, H, NP, WM, WN, CST>;
+  static_assert(!DYN || ((ABL & ~256) == 0 && C::DEEP && C::NCC % 2 == 0),
+                "claimed tiles: the two-stage producer body, whole bodies per tile, no ablation");
   constexpr int TR = C::TR;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -104,9 +113,13 @@ __global__ __launch_bounds__((WM * WN + 4) * 64) void k_conv_w1(const float* __r
   const int my_tiles = rb < ntiles ? (ntiles - 1 - rb) / nwg + 1 : 0;
   const int NS = my_tiles * C::NCC;
   if (NS == 0) return;
+  if constexpr ((ABL & 256) != 0) {
+    if (tid == 0) stamps[2 * blockIdx.x] = (long long)__builtin_amdgcn_s_memrealtime();
+  }
   char* const buf0 = smem;
   char* const buf1 = smem + C::BUF;
-  auto tile_of = [&](int s) { return (rb + (s / C::NCC) * nwg) * NP; };  // first patch of stage s's tile
+  int* const tq = reinterpret_cast<int*>(smem + C::TQ_OFF);
+  auto tile_of = [&](int s) { return (rb + (s / C::NCC) * nwg) * NP; };  // first patch of stage s's tile (static)
 
   // ---- producer side ----
   // A unit (patch, window row, column pair t, 8-channel group) loads input columns 2t - 1 and 2t (the
@@ -119,11 +132,14 @@ __global__ __launch_bounds__((WM * WN + 4) * 64) void k_conv_w1(const float* __r
   // vmcnt accounting stays exact and stage s + 1's write waits only for stage s + 1's loads (with
   // if-guarded global loads it waited vmcnt(0), i.e. also for the stage s + 2 loads just issued).
   constexpr unsigned PATCH_BYTES = (unsigned)H * H * CIN * 4, OOB = 0x80000000u;
-  auto produce_loads = [&](int s, float4 (&d)[C::UPT][6]) {
-    // a stage past the last one (the loops below issue it unconditionally) gets an empty resource
-    const bool live = s < NS;
-    const int p0 = live ? tile_of(s) : 0;
-    const int cc = s % C::NCC;
+  // chunk cc of work tile `tile` (hn_tiles::kEnd: a stage past the last one -- the loops below issue it
+  // unconditionally -- gets an empty resource)
+  auto produce_loads_at = [&](int tile, int cc, float4 (&d)[C::UPT][6]) {
+    // (DYN: the tile index pinned to an SGPR, or the buffer resource ends up in VGPRs and every load in a
+    // waterfall loop)
+    if constexpr (DYN) tile = __builtin_amdgcn_readfirstlane(tile);
+    const bool live = tile != hn_tiles::kEnd;
+    const int p0 = live ? tile * NP : 0;
     const int nval = !live ? 0 : P - p0 < NP ? P - p0 : NP;
     const __amdgpu_buffer_rsrc_t rs = make_rsrc(in + (size_t)p0 * H * H * CIN, (unsigned)nval * PATCH_BYTES);
 #pragma unroll
@@ -184,6 +200,9 @@ __global__ __launch_bounds__((WM * WN + 4) * 64) void k_conv_w1(const float* __r
       }
     }
   };
+  auto produce_loads = [&](int s, float4 (&d)[C::UPT][6]) {  // static tiling: stage s of the flat sequence
+    produce_loads_at(s < NS ? rb + (s / C::NCC) * nwg : hn_tiles::kEnd, s % C::NCC, d);
+  };
 
   // the zero rows (both buffers, both planes): what every padding-row operand read returns
   for (int i = tid; i < 4 * C::RS / 16; i += C::NTHR) {
@@ -206,6 +225,45 @@ __global__ __launch_bounds__((WM * WN + 4) * 64) void k_conv_w1(const float* __r
     // Loads and writes are unconditional (a stage past NS loads zeros from an empty resource and is
     // written into the buffer nobody reads again): any branch around them makes the compiler's vmcnt
     // merge conservative, and a vmcnt(0) here also waits for the loads issued one stage ahead.
+    if constexpr (DYN) {
+      // The static loop below, per claimed tile: an iteration is the tile's NCC stages (NCC / 2 two-stage
+      // bodies; stage j counts from the running tile's first, so j >= NCC is the next tile's).  Lane 0 issues
+      // the claim of tile k + 2 at the head of iteration k and publishes it ahead of the iteration's last
+      // barrier; the cursor moves behind that barrier, as the MFMA waves' does.
+      hn_tiles::DeviceCounter ctr{tile_ctr};
+      hn_tiles::Claimer cl = hn_tiles::claimer(ptid == 0);
+      if (ptid == 0) hn_tiles::ring_init(tq, rb, nwg, ntiles);
+      produce_loads_at(rb, 0, pf);
+      produce_write(buf0, pf);
+      produce_loads_at(rb, 1, pf);
+      __syncthreads();
+      // (tile indices wave-uniform in SGPRs: the loads' buffer resources are built from them)
+      hn_tiles::Cursor c;
+      hn_tiles::cursor_start(c, tq);
+      c.cur = __builtin_amdgcn_readfirstlane(c.cur);
+      c.nxt = __builtin_amdgcn_readfirstlane(c.nxt);
+#pragma unroll 1
+      while (!hn_tiles::cursor_done(c)) {
+        hn_tiles::claim_issue(cl, ctr);
+#pragma unroll 1
+        for (int j = 0; j < C::NCC; j += 2) {
+          produce_loads_at(hn_tiles::stage_tile(c, j + 2, C::NCC), hn_tiles::stage_chunk(j + 2, C::NCC), pf2);
+          produce_write(buf1, pf);
+          __syncthreads();
+          produce_loads_at(hn_tiles::stage_tile(c, j + 3, C::NCC), hn_tiles::stage_chunk(j + 3, C::NCC), pf);
+          produce_write(buf0, pf2);
+          if (j + 2 == C::NCC) {
+            const int t = hn_tiles::claim_settle(cl, ctr, nwg, ntiles);
+            if (ptid == 0) tq[hn_tiles::slot(c.k + 2)] = t;
+          }
+          __syncthreads();
+        }
+        hn_tiles::cursor_advance(c, tq);
+        c.nxt = __builtin_amdgcn_readfirstlane(c.nxt);
+      }
+      hn_tiles::claim_finish(cl, ctr, nwg);
+      return;
+    }
     produce_loads(0, pf);
     produce_write(buf0, pf);
     produce_loads(1, pf);
@@ -387,9 +445,16 @@ __global__ __launch_bounds__((WM * WN + 4) * 64) void k_conv_w1(const float* __r
 #pragma unroll
     for (int i = 0; i < 16; ++i) y1a[1][i] = ssub(y1a[1][i], ma[1][i]);
   };
+  // DYN: the tile sequence comes from the ring (the producers' cursor, behind the same barriers); a stage's
+  // buffer is its chunk's parity (NCC is even), so the static stage numbers below stand
+  hn_tiles::Cursor c{0, 0, 0};
+  if constexpr (DYN) {
+    hn_tiles::cursor_start(c, tq);
+    c.cur = __builtin_amdgcn_readfirstlane(c.cur);
+  }
 #pragma unroll 1
-  for (int t = 0; t < my_tiles; ++t) {
-    const int s0 = t * C::NCC, s = s0 + C::NCC - 1;  // the work tile's first and last stage
+  for (int t = 0; DYN ? !hn_tiles::cursor_done(c) : t < my_tiles; ++t) {
+    const int s0 = DYN ? 0 : t * C::NCC, s = s0 + C::NCC - 1;  // the work tile's first and last stage
     stage(std::true_type{}, s0, 0, C::NCC > 1 ? 1 : 0);
 #pragma unroll 1
     for (int cc = 1; cc < C::NCC; ++cc) {
@@ -398,7 +463,7 @@ __global__ __launch_bounds__((WM * WN + 4) * 64) void k_conv_w1(const float* __r
     }
     if constexpr ((ABL & 2) == 0) fold_last();
     {
-      const int p0 = tile_of(s);
+      const int p0 = DYN ? c.cur * NP : tile_of(s);
       // the epilogue re-derives its per-lane address terms from an opaque lane id once per work tile: kept in
       // registers across the stages they push the K-loop over the register budget
       int le = lane;
@@ -452,16 +517,34 @@ __global__ __launch_bounds__((WM * WN + 4) * 64) void k_conv_w1(const float* __r
       }
     }
     __syncthreads();
+    if constexpr (DYN) {
+      hn_tiles::cursor_advance(c, tq);
+      c.cur = __builtin_amdgcn_readfirstlane(c.cur);
+    }
+  }
+  if constexpr ((ABL & 256) != 0) {
+    if (tid == 0) stamps[2 * blockIdx.x + 1] = (long long)__builtin_amdgcn_s_memrealtime();
   }
 }
 
-// A table row's launcher: conv layer L (3 / 5) at weight ring depth WD, ablation build ABL
+// A table row's launcher: conv layer L (3 / 5) at weight ring depth WD, ablation build ABL.  The production rows
+// (ABL 0) claim their tiles when the calling forward has counters (hn_tile_counters), else tile statically.
 template <int L, int CIN, int COUT, int H, int NP, int WM, int WN, bool CST, int WD, int ABL>
 hipError_t launch_w1(const HardnetDev& d, const float* in, float* out, int P, float, hipStream_t st) {
   using C = W1Cfg<CIN, COUT, H, NP, WM, WN, CST>;
   if (!d.wino1[L]) return hipErrorInvalidValue;
+  const uint4* w = static_cast<const uint4*>(d.wino1[L]);
+  long long* stamps = nullptr;
+  if constexpr ((ABL & 256) != 0)  // past a full chunk's workspace, behind k_c12s's 2 MiB (tools/tail_timeline.py)
+    stamps = reinterpret_cast<long long*>((L == 3 ? out + (size_t)P * 40960 : const_cast<float*>(in) + (size_t)P * 24576) +
+                                          (2 << 20) / 4) + (L == 3 ? 0 : 2048);
+  if constexpr ((ABL & ~256) == 0) {
+    if (unsigned* ctr = hn_tile_counters(L == 3 ? kTilesConv3 : kTilesConv5))
+      return hn_launch_persistent<&k_conv_w1<CIN, COUT, H, NP, WM, WN, CST, WD, ABL, true>, C::NTHR, C::SMEM>(
+          (P + NP - 1) / NP, st, in, out, w, d.bias[L], P, ctr, stamps);
+  }
   return hn_launch_persistent<&k_conv_w1<CIN, COUT, H, NP, WM, WN, CST, WD, ABL>, C::NTHR, C::SMEM>(
-      (P + NP - 1) / NP, st, in, out, static_cast<const uint4*>(d.wino1[L]), d.bias[L], P);
+      (P + NP - 1) / NP, st, in, out, w, d.bias[L], P, (unsigned*)nullptr, stamps);
 }
 
 #ifdef HN_EXPERIMENTS  // F(4,3) conv3 (k_conv_w4): measured slower than k_conv_w1 (11.2 vs 9.9 ms), experiments library only
@@ -865,6 +948,8 @@ constexpr HnConvRow kWino1Rows[] = {
     {5, 34, w1c5<8, 64>},
     {3, 35, w1c3<8, 128>},
     {5, 35, w1c5<8, 128>},
+    {3, 27, w1c3<8, 256>},  // r: the defaults (q / l) with start / end stamps per workgroup (right results)
+    {5, 27, w1c5<6, 256>},
     {3, 32, launch_w4c3<6>},  // w / x: conv3 as F(4,3) (k_conv_w4), weight ring 6 / 9
     {3, 33, launch_w4c3<9>},
 #endif

@@ -101,7 +101,20 @@ int hn_create(const hn_arch_desc* desc, const float* host_params, size_t n_param
  * HN_PIPELINE=1 (opt-in) overlaps a multi-chunk HardNet batch's chunks over a second, internally created
  * stream (forked from and joined back into hip_stream, so graph capture holds) and adds one more
  * chunk x 64 KiB buffer for batches of more than one chunk.
- * NAS / FDL descriptors need four buffers of their largest per-patch activation. */
+ * NAS / FDL descriptors need four buffers of their largest per-patch activation.
+ *
+ * Work-tile counters (stock HardNet).  The persistent conv3 / conv5 kernels claim their work tiles from
+ * counters in a small allocation the model owns (made and zeroed by hn_create, freed by hn_destroy; no part
+ * of the workspace, and no stream operation per call: the kernels leave the counters at zero).  Each forward
+ * call takes the next of HN_TILE_RING counter blocks in rotation, so what the ring bounds is: at most
+ * HN_TILE_RING forward calls of ONE model may be in flight on DIFFERENT streams at a time -- calls on one
+ * stream run in order and may share a block, however many are queued.  A call made while its stream is being
+ * captured takes one of HN_TILE_CAPTURES further blocks for good (a graph may be replayed at any later time,
+ * beside eager calls); the model's captures past that number, and every call if the allocation failed, use
+ * the static tile assignment.  HN_STATIC_TILES=1 (read by hn_create) selects the static assignment
+ * everywhere: the same descriptors, bit for bit. */
+#define HN_TILE_RING 64
+#define HN_TILE_CAPTURES 64
 int hn_workspace_bytes(const hn_model* m, int64_t batch, size_t* bytes_out);
 
 /* d_in: [B,1,32,32] fp32 contiguous (device); d_out: [B,128] fp32 (device).
