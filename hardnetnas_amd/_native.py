@@ -58,7 +58,8 @@ EXPORTED = ["hn_param_count", "hn_create", "hn_workspace_bytes", "hn_forward",
             "hn_neimask_loss_backward", "hn_fpr95_workspace_bytes",
             "hn_fpr95", "hn_match_workspace_bytes", "hn_match_nn2", "hn_clip_patch", "hn_workspace_bytes_kp",
             "hn_forward_kp", "hn_det_param_count", "hn_det_create", "hn_det_workspace_bytes", "hn_det_forward",
-            "hn_det_destroy", "hn_select_workspace_bytes", "hn_select_keypoints", "hn_preprocess", "hn_set_profiling",
+            "hn_det_destroy", "hn_select_workspace_bytes", "hn_select_keypoints", "hn_warp_score", "hn_gt_scale_orin",
+            "hn_mask_keypoints", "hn_project_keypoints", "hn_preprocess", "hn_set_profiling",
             "hn_stage_times", "hn_destroy", "hn_last_error", "hn_abi_version"]
 
 
@@ -126,6 +127,10 @@ def load_library():
         lib.hn_select_workspace_bytes.argtypes = [I64, I32, I32, I32, ctypes.POINTER(S)]
         lib.hn_select_keypoints.argtypes = [P, I64, I32, I32, I32, F32, I32, I32, I32, F32, P, F32, P, P, P, P, P, P, P,
                                             P, S, P]
+        lib.hn_warp_score.argtypes = [P, P, I64, I32, I32, I32, I32, P, P, P]
+        lib.hn_gt_scale_orin.argtypes = [P, F32, P, P, P, I64, I32, I32, P, P, P]
+        lib.hn_mask_keypoints.argtypes = [P, I64, I32, I32, I32, P, F32, P, P, P, P, P, P]
+        lib.hn_project_keypoints.argtypes = [P, I64, P, I64, I32, I32, P, F32, P, I32, P, P, P, P]
         lib.hn_preprocess.argtypes = [P, I64, I32, I32, I32, ctypes.c_float, ctypes.c_float, P, P]
         lib.hn_set_profiling.argtypes = [P, ctypes.c_int]
         lib.hn_stage_times.argtypes = [P, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p),
@@ -145,7 +150,8 @@ def load_library():
                      "hn_neimask_loss_forward", "hn_neimask_loss_backward", "hn_match_workspace_bytes",
                      "hn_match_nn2", "hn_clip_patch", "hn_workspace_bytes_kp", "hn_forward_kp",
                      "hn_det_param_count", "hn_det_create", "hn_det_workspace_bytes", "hn_det_forward",
-                     "hn_select_workspace_bytes", "hn_select_keypoints"):
+                     "hn_select_workspace_bytes", "hn_select_keypoints", "hn_warp_score", "hn_gt_scale_orin",
+                     "hn_mask_keypoints", "hn_project_keypoints"):
             getattr(lib, name).restype = ctypes.c_int
         if lib.hn_abi_version() != ABI_VERSION:
             raise RuntimeError(f"{path}: ABI version {lib.hn_abi_version()}, expected {ABI_VERSION}; rebuild it")
@@ -787,6 +793,121 @@ def select_keypoints(score: torch.Tensor, border: int, nms_thresh: float, nms_ks
                                        ptr(out.get("score_proc")), ptr(out.get("topk_mask")), workspace.data_ptr(),
                                        workspace.numel(), stream), "hn_select_keypoints")
     return out
+
+
+# ----------------------------------------------------------------------------------
+# homography ground-truth stage (hn_gt.hip)
+# ----------------------------------------------------------------------------------
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _gt_map(name, t, shape, dev, dtype=torch.float32):
+    """``t`` as the contiguous ``dtype`` tensor of ``shape`` on ``dev`` that the C ABI reads (None stays None)."""
+    if t is None:
+        return None
+    if not t.is_cuda or t.device != dev or t.dtype != dtype or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must be a {dtype} HIP tensor {tuple(shape)} on {dev}, got {t.dtype} "
+                         f"{tuple(t.shape)} on {t.device}")
+    return t.contiguous()
+
+
+def _gt_homo(name, h, b, dev):
+    if not h.is_cuda or h.device != dev or h.dtype != torch.float32 or h.numel() != 9 * b:
+        raise ValueError(f"{name} must be fp32 [{b},3,3] on {dev}, got {h.dtype} {tuple(h.shape)} on {h.device}")
+    return h.contiguous().view(b, 9)
+
+
+def warp_score(score: torch.Tensor, homo: torch.Tensor, border: int = 8, align_corners: bool = False,
+               want_warped: bool = True, want_visible: bool = True):
+    """gtscore's two warps in one kernel (hn_warp_score): score fp32 [B,H,W] and homo fp32 [B,3,3] on one HIP device
+    -> (warped [B,H,W], visible [B,H,W]); the source reads as 0 within ``border`` pixels of an edge."""
+    lib = load_library()
+    if not score.is_cuda or score.dtype != torch.float32 or score.dim() != 3:
+        raise ValueError(f"score must be a fp32 HIP tensor [B,H,W], got {score.dtype} {tuple(score.shape)}")
+    dev = score.device
+    s = score.contiguous()
+    b, h, w = s.shape
+    hm = _gt_homo("homo", homo, b, dev)
+    warped = torch.empty((b, h, w), device=dev, dtype=torch.float32) if want_warped else None
+    visible = torch.empty((b, h, w), device=dev, dtype=torch.float32) if want_visible else None
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        _check(lib.hn_warp_score(s.data_ptr(), hm.data_ptr(), b, h, w, int(border), int(bool(align_corners)),
+                                 _ptr(warped), _ptr(visible), stream), "hn_warp_score")
+    return warped, visible
+
+
+def gt_scale_orin(scale_map: Optional[torch.Tensor], ori_map: torch.Tensor, homo12: torch.Tensor,
+                  homo21: torch.Tensor, scale_value: float = 32.0):
+    """Network.gt_scale_orin in one kernel (hn_gt_scale_orin): ori_map fp32 [B,H,W,2], scale_map fp32 [B,H,W] or None
+    (then ``scale_value`` everywhere), homographies fp32 [B,3,3] -> (gt_scale [B,H,W], gt_ori [B,H,W,2])."""
+    lib = load_library()
+    if not ori_map.is_cuda or ori_map.dtype != torch.float32 or ori_map.dim() != 4 or ori_map.shape[3] != 2:
+        raise ValueError(f"ori_map must be a fp32 HIP tensor [B,H,W,2], got {ori_map.dtype} {tuple(ori_map.shape)}")
+    dev = ori_map.device
+    om = ori_map.contiguous()
+    b, h, w, _ = om.shape
+    sm = _gt_map("scale_map", scale_map, (b, h, w), dev)
+    h12, h21 = _gt_homo("homo12", homo12, b, dev), _gt_homo("homo21", homo21, b, dev)
+    gt_scale = torch.empty((b, h, w), device=dev, dtype=torch.float32)
+    gt_ori = torch.empty((b, h, w, 2), device=dev, dtype=torch.float32)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        _check(lib.hn_gt_scale_orin(_ptr(sm), float(scale_value), om.data_ptr(), h12.data_ptr(), h21.data_ptr(), b, h,
+                                    w, gt_scale.data_ptr(), gt_ori.data_ptr(), stream), "hn_gt_scale_orin")
+    return gt_scale, gt_ori
+
+
+def mask_keypoints(mask: torch.Tensor, topk: int, scale_map: Optional[torch.Tensor] = None, scale_value: float = 32.0,
+                   ori_map: Optional[torch.Tensor] = None, want_counts: bool = False):
+    """pair's nonzero() and masked_selects (hn_mask_keypoints): mask uint8 [B,H,W] -> (kpts [B K,4] int64 rows
+    (b, y, x, 0) in raster order, kscale [B K], kori [B K,2] or None, counts [B] int32 or None).  An image with fewer
+    than K set pixels gets rows (b, 0, 0, 0) for the rest; nothing is read back."""
+    lib = load_library()
+    if not mask.is_cuda or mask.dtype != torch.uint8 or mask.dim() != 3:
+        raise ValueError(f"mask must be a uint8 HIP tensor [B,H,W], got {mask.dtype} {tuple(mask.shape)}")
+    dev = mask.device
+    m = mask.contiguous()
+    b, h, w = m.shape
+    sm = _gt_map("scale_map", scale_map, (b, h, w), dev)
+    om = _gt_map("ori_map", ori_map, (b, h, w, 2), dev)
+    n = b * int(topk)
+    kpts = torch.empty((max(n, 0), 4), device=dev, dtype=torch.int64)
+    kscale = torch.empty(max(n, 0), device=dev, dtype=torch.float32)
+    kori = torch.empty((max(n, 0), 2), device=dev, dtype=torch.float32) if om is not None else None
+    counts = torch.empty(b, device=dev, dtype=torch.int32) if want_counts else None
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        _check(lib.hn_mask_keypoints(m.data_ptr(), b, h, w, int(topk), _ptr(sm), float(scale_value), _ptr(om),
+                                     kpts.data_ptr(), kscale.data_ptr(), _ptr(kori), _ptr(counts), stream),
+               "hn_mask_keypoints")
+    return kpts, kscale, kori, counts
+
+
+def project_keypoints(kpts: torch.Tensor, homo: torch.Tensor, shape, scale_map: Optional[torch.Tensor] = None,
+                      scale_value: float = 32.0, ori_map: Optional[torch.Tensor] = None, clamp: bool = True):
+    """ptCltoCr (hn_project_keypoints): kpts int64 [N,4] rows (b, y, x, .), homo fp32 [B,3,3], ``shape`` = (B, H, W) of
+    the right image's maps -> (kpts_r [N,4] rows (b, y', x', 0), scale_r [N], ori_r [N,2] or None)."""
+    lib = load_library()
+    if not kpts.is_cuda or kpts.dtype != torch.int64 or kpts.dim() != 2 or kpts.shape[1] != 4:
+        raise ValueError(f"kpts must be an int64 HIP tensor [N,4], got {kpts.dtype} {tuple(kpts.shape)}")
+    dev = kpts.device
+    kp = kpts.contiguous()
+    b, h, w = (int(v) for v in shape)
+    hm = _gt_homo("homo", homo, b, dev)
+    sm = _gt_map("scale_map", scale_map, (b, h, w), dev)
+    om = _gt_map("ori_map", ori_map, (b, h, w, 2), dev)
+    n = kp.shape[0]
+    kpts_r = torch.empty((n, 4), device=dev, dtype=torch.int64)
+    scale_r = torch.empty(n, device=dev, dtype=torch.float32)
+    ori_r = torch.empty((n, 2), device=dev, dtype=torch.float32) if om is not None else None
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        _check(lib.hn_project_keypoints(kp.data_ptr(), n, hm.data_ptr(), b, h, w, _ptr(sm), float(scale_value),
+                                        _ptr(om), int(bool(clamp)), kpts_r.data_ptr(), scale_r.data_ptr(),
+                                        _ptr(ori_r), stream), "hn_project_keypoints")
+    return kpts_r, scale_r, ori_r
 
 
 RESIZE_MODES = {"none": 0, "cv2": 1, "pil": 2}  # enum hn_resize

@@ -1705,6 +1705,79 @@ extern "C" int hn_select_keypoints(const float* d_score, int64_t n_images, int32
   return HN_OK;
 }
 
+// homography ground-truth stage (hn_gt.hip): what the four calls check about the maps before the GPU is touched;
+// null = fine.  height * width < 2^31 and n_images * height * width < 2^62 are hn_homo.h's conditions.
+static const char* gt_arg_error(int64_t n_images, int32_t height, int32_t width) {
+  if (n_images < 0) return "n_images must be >= 0";
+  if (height < 2 || width < 2) return "height and width must be >= 2";
+  if ((int64_t)height * width > INT32_MAX) return "height * width must be below 2^31";
+  if (n_images > ((int64_t)1 << 62) / ((int64_t)height * width)) return "n_images * height * width must be below 2^62";
+  return nullptr;
+}
+
+extern "C" int hn_warp_score(const float* d_score, const float* d_homo, int64_t n_images, int32_t height,
+                             int32_t width, int32_t border, int32_t align_corners, float* d_warped, float* d_visible,
+                             void* hip_stream) {
+  if (const char* e = gt_arg_error(n_images, height, width)) return fail(HN_ERR_ARG, e);
+  if (border < 0 || height <= 2 * (int64_t)border || width <= 2 * (int64_t)border)
+    return fail(HN_ERR_ARG, "border must be >= 0 with height, width > 2 * border");
+  if (align_corners != 0 && align_corners != 1) return fail(HN_ERR_ARG, "align_corners must be 0 or 1");
+  if (n_images == 0 || (!d_warped && !d_visible)) return HN_OK;
+  if (!d_homo || (d_warped && !d_score))
+    return fail(HN_ERR_ARG, "NULL device pointer (d_warped or d_visible may be; d_score only without d_warped)");
+  HIPCHK(hn_launch_warp_score(d_score, d_homo, n_images, height, width, border, align_corners, d_warped, d_visible,
+                              static_cast<hipStream_t>(hip_stream)));
+  return HN_OK;
+}
+
+extern "C" int hn_gt_scale_orin(const float* d_scale, float scale_value, const float* d_ori, const float* d_homo12,
+                                const float* d_homo21, int64_t n_images, int32_t height, int32_t width,
+                                float* d_gt_scale, float* d_gt_ori, void* hip_stream) {
+  if (const char* e = gt_arg_error(n_images, height, width)) return fail(HN_ERR_ARG, e);
+  if (n_images == 0) return HN_OK;
+  if (!d_ori || !d_homo12 || !d_homo21 || !d_gt_scale || !d_gt_ori)
+    return fail(HN_ERR_ARG, "NULL device pointer (only d_scale may be NULL)");
+  if ((reinterpret_cast<uintptr_t>(d_ori) | reinterpret_cast<uintptr_t>(d_gt_ori)) & 7)
+    return fail(HN_ERR_ARG, "d_ori and d_gt_ori must be 8-byte aligned");
+  HIPCHK(hn_launch_gt_scale_orin(d_scale, scale_value, d_ori, d_homo12, d_homo21, n_images, height, width, d_gt_scale,
+                                 d_gt_ori, static_cast<hipStream_t>(hip_stream)));
+  return HN_OK;
+}
+
+extern "C" int hn_mask_keypoints(const uint8_t* d_mask, int64_t n_images, int32_t height, int32_t width, int32_t topk,
+                                 const float* d_scale_map, float scale_value, const float* d_ori_map, int64_t* d_kpts,
+                                 float* d_kscale, float* d_kori, int32_t* d_counts, void* hip_stream) {
+  if (const char* e = gt_arg_error(n_images, height, width)) return fail(HN_ERR_ARG, e);
+  if (topk < 1 || topk > (int64_t)height * width) return fail(HN_ERR_ARG, "topk must be in 1 .. height * width");
+  if (n_images > INT64_MAX / 8 / topk) return fail(HN_ERR_ARG, "n_images * topk too large");
+  if ((d_kori == nullptr) != (d_ori_map == nullptr))
+    return fail(HN_ERR_ARG, "d_kori and d_ori_map must both be given or both NULL");
+  if (n_images == 0) return HN_OK;
+  if (!d_mask || !d_kpts || !d_kscale)
+    return fail(HN_ERR_ARG, "NULL device pointer (d_scale_map, d_ori_map / d_kori and d_counts may be)");
+  HIPCHK(hn_launch_mask_keypoints(d_mask, n_images, height, width, topk, d_scale_map, scale_value, d_ori_map, d_kpts,
+                                  d_kscale, d_kori, d_counts, static_cast<hipStream_t>(hip_stream)));
+  return HN_OK;
+}
+
+extern "C" int hn_project_keypoints(const int64_t* d_kpts, int64_t n, const float* d_homo, int64_t n_images,
+                                    int32_t height, int32_t width, const float* d_scale_map, float scale_value,
+                                    const float* d_ori_map, int32_t clamp, int64_t* d_kpts_r, float* d_scale_r,
+                                    float* d_ori_r, void* hip_stream) {
+  if (n < 0) return fail(HN_ERR_ARG, "n must be >= 0");
+  if (const char* e = gt_arg_error(n_images, height, width)) return fail(HN_ERR_ARG, e);
+  if (n > 0 && n_images == 0) return fail(HN_ERR_ARG, "n_images must be >= 1 for n > 0 keypoints");
+  if (clamp != 0 && clamp != 1) return fail(HN_ERR_ARG, "clamp must be 0 or 1");
+  if ((d_ori_r == nullptr) != (d_ori_map == nullptr))
+    return fail(HN_ERR_ARG, "d_ori_r and d_ori_map must both be given or both NULL");
+  if (n == 0) return HN_OK;
+  if (!d_kpts || !d_homo || !d_kpts_r || !d_scale_r)
+    return fail(HN_ERR_ARG, "NULL device pointer (d_scale_map and d_ori_map / d_ori_r may be)");
+  HIPCHK(hn_launch_project_kpts(d_kpts, n, d_homo, n_images, height, width, d_scale_map, scale_value, d_ori_map, clamp,
+                                d_kpts_r, d_scale_r, d_ori_r, static_cast<hipStream_t>(hip_stream)));
+  return HN_OK;
+}
+
 // ---------------------------------------------------------------------------------------
 // train-mode stock HardNet (hn_train.hip)
 // ---------------------------------------------------------------------------------------

@@ -282,6 +282,18 @@ struct HnSelectArgs {
 };
 size_t hn_select_ws_bytes(int64_t B, int H, int W);
 hipError_t hn_launch_select(const HnSelectArgs& a, hipStream_t st);
+// homography ground-truth stage (hn_gt.hip): warp + visibility, gt_scale_orin, mask -> keypoints, ptCltoCr
+hipError_t hn_launch_warp_score(const float* score, const float* homo, int64_t B, int H, int W, int border,
+                                int align_corners, float* warped, float* visible, hipStream_t st);
+hipError_t hn_launch_gt_scale_orin(const float* scale, float scale_value, const float* ori, const float* homo12,
+                                   const float* homo21, int64_t B, int H, int W, float* gt_scale, float* gt_ori,
+                                   hipStream_t st);
+hipError_t hn_launch_mask_keypoints(const uint8_t* mask, int64_t B, int H, int W, int K, const float* scale_map,
+                                    float scale_value, const float* ori_map, int64_t* kpts, float* kscale, float* kori,
+                                    int32_t* counts, hipStream_t st);
+hipError_t hn_launch_project_kpts(const int64_t* kpts, int64_t n, const float* homo, int64_t B, int H, int W,
+                                  const float* scale_map, float scale_value, const float* ori_map, int clamp,
+                                  int64_t* kpts_r, float* scale_r, float* ori_r, hipStream_t st);
 hipError_t hn_launch_loss(const float* pos, const float* rmin, const float* cmin, int n, float margin,
                           int type, float scale, float* min_neg, float* loss, hipStream_t st);
 

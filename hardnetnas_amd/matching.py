@@ -7,6 +7,7 @@ of FDLNet-master/latency/NASNet/utils/eval_utils.py:
     nearest_neighbor_threshold_match_score        :129-148
     nearest_neighbor_distance_ratio_match         :168-175
     nearest_neighbor_distance_ratio_match_score   :178-197
+    eval_model                                    :85-109
 
 and ``distance_matrix_vector`` of utils/math_utils.py:8-19.  The reference builds the N x M distance
 matrix and takes its row ``min`` or ``sort``; here fp32 [., 128] descriptors on a HIP device go through
@@ -103,3 +104,21 @@ def nearest_neighbor_distance_ratio_match_score(des1, des2, kp1w, kp2, visible, 
     predicted = predicted & visible
     correct = predicted & _within_reach(kp1w, nn_kp2, COO_THRSH) & visible
     return _count(correct), max(_count(predicted), 1)
+
+
+def eval_model(model, parsed_batch, DES_THRSH, COO_THRSH):
+    """``(TPNN, PNN, TPNNT, PNNT, TPNNDR, PNNDR)`` of one image pair (eval_utils.py:85-109; batch size 1, as there):
+    ``model.inference`` on both images, image 1's keypoints projected into image 2 unclamped
+    (``network.ptCltoCr(clamp=False)``), then the three match scores above.  With a ``network.Network`` on HIP
+    tensors every step before the counts runs on the library's kernels."""
+    from .network import ptCltoCr
+    im1_data, im1_info, homo12, im2_data, im2_info, homo21, im1_raw, im2_raw = parsed_batch
+    scale1, kp1, des1, _, _, _ = model.inference(im1_data, im1_info, im1_raw)
+    scale2, kp2, des2, _, _, _ = model.inference(im2_data, im2_info, im2_raw)
+    kp1w = ptCltoCr(kp1, homo12, scale2, right_imorint=None, clamp=False)[0]
+    _, _, maxh, maxw = im2_data.size()
+    visible = kp1w[:, 2].lt(maxw) * kp1w[:, 1].lt(maxh)
+    TPNN, PNN = nearest_neighbor_match_score(des1, des2, kp1w, kp2, visible, COO_THRSH)
+    TPNNT, PNNT = nearest_neighbor_threshold_match_score(des1, des2, kp1w, kp2, visible, DES_THRSH, COO_THRSH)
+    TPNNDR, PNNDR = nearest_neighbor_distance_ratio_match_score(des1, des2, kp1w, kp2, visible, COO_THRSH)
+    return TPNN, PNN, TPNNT, PNNT, TPNNDR, PNNDR

@@ -377,6 +377,69 @@ int hn_select_keypoints(const float* d_score, int64_t n_images, int32_t height, 
                         float* d_kscore, float* d_kscale, float* d_kori, float* d_score_proc, uint8_t* d_topk_mask,
                         void* d_workspace, size_t workspace_bytes, void* hip_stream);
 
+/* The homography ground-truth stage of Network.forward (model/network.py:23-142, 185-264): what lies between the
+ * detector's maps of an image pair and its patch pairs.  Homographies are device arrays [n_images, 9] fp32, row-major
+ * 3x3, as the batch holds them; maps are dense [n_images,height,width(,2)] fp32.  One projection is used everywhere:
+ *   u = h00 x + h01 y + h02, v = h10 x + h11 y + h12, w = h20 x + h21 y + h22 -> (u / (w + 1e-8), v / (w + 1e-8)),
+ * products summed left to right without contraction, IEEE divisions.  .long() truncates toward zero and .round()
+ * rounds half to even; before either conversion a NaN becomes 0 and the value saturates (truncation at +-(2^30 - 64),
+ * rounding at +-(2^31 - 128): every image has fewer than 2^31 pixels, so such a coordinate is outside it either way).
+ * All four calls: caller's stream, one kernel launch, no allocation, workspace or synchronisation inside
+ * (capturable), no float atomics; an image's result is bit-identical call to call and independent of what else is
+ * in the batch.  Bounds guarantee: no byte outside the inputs is read whatever the homography, keypoint, map or mask
+ * data holds (the address computations are hn_homo.h's, swept on the host by `make homo_check`).  Every argument
+ * check runs before the GPU is touched: n_images >= 0 (0 returns HN_OK), height, width >= 2, height * width < 2^31,
+ * n_images * height * width < 2^62; else HN_ERR_ARG.
+ *
+ * hn_warp_score -- gtscore's two warp calls with filter_border fused into the read (utils/image_utils.py:161-213).
+ *   Output pixel (x, y) is projected by d_homo to (px, py); xn = px / (W - 1) * 2 - 1, yn likewise with H; then
+ *   grid_sample's bilinear sampling with zeros padding: ix = ((xn + 1) W - 1) / 2 (align_corners 0) or
+ *   (xn + 1) / 2 (W - 1) (align_corners 1), corners floor(ix) and floor(ix) + 1, unclamped, the four weights from the
+ *   unclamped corners, a corner outside the image contributing 0.  The source value reads as 0 within `border`
+ *   pixels of an edge (8 in the reference; 0 = no filter).  d_warped = the sample of d_score, d_visible = the same
+ *   sample of a map of ones (the sum of the in-bounds weights, no border); either may be NULL.
+ *   Deliberate note on align_corners: the reference calls grid_sample without the argument, which in today's torch
+ *   means False, so 0 is "what the reference's code does" (and under 0 the identity homography is not an identity
+ *   warp); 1 is the behaviour its (W - 1) normalisation was written for.  Both are supported.
+ *   Also needs border >= 0 with height, width > 2 border and align_corners in {0, 1}.
+ *
+ * hn_gt_scale_orin -- Network.gt_scale_orin (model/network.py:200-264) with no intermediate map.  The reference
+ *   computes centScale, cos_w, sin_w at every pixel of image 2 and gathers them at q = clamp(round(proj(homo12, p)));
+ *   here output pixel p computes q first and evaluates the formulas at q only.  With s = d_scale[q] (or scale_value
+ *   where d_scale is NULL) and h = floor(s / 2): the centre q and (qx, qy -+ h), (qx +- h, qy) are projected by homo21
+ *   and truncated; each distance is 2 sqrt(float(dx^2 + dy^2) + 1e-8); d_gt_scale = (up + right + bottom + left) / 4
+ *   in that order.  Orientation: (qx + s cos, qy + s sin) and the centre projected, untruncated; ww, hw their
+ *   differences; r = sqrt(ww^2 + hw^2 + 1e-8); (ww / (r + 1e-8), hw / (r + 1e-8)) divided by that pair's L2 norm (no
+ *   epsilon).  d_ori and d_gt_ori [n_images,height,width,2] (cos, sin), 8-byte aligned.
+ *
+ * hn_mask_keypoints -- pair's left_imtopk.nonzero() and masked_selects (utils/net_utils.py:27-37) for a top-K mask
+ *   d_mask [n_images,height,width] uint8 (hn_select_keypoints' d_topk_mask: pair uses the FIRST top-K mask, not the
+ *   keypoints of the second): d_kpts [n_images topk, 4] int64 rows (b, y, x, 0), the first topk set pixels of every
+ *   image in raster order, images in order; d_kscale / d_kori gathered from the maps (or scale_value; d_kori and
+ *   d_ori_map both or neither).  An image with fewer set pixels gets rows (b, 0, 0, 0) for the rest (scale and
+ *   orientation of its pixel (0, 0)); the count is never read back.  d_counts [n_images] int32 (or NULL) receives the
+ *   true number of set pixels.  The compaction is a scan, not an atomic append.  1 <= topk <= height * width.
+ *
+ * hn_project_keypoints -- ptCltoCr (utils/math_utils.py:43-106): d_kpts [n,4] rows (b, y, x, .) -> d_kpts_r [n,4]
+ *   rows (b, y', x', 0) with (x', y') = round(proj(d_homo[b], (x, y))), clamped to [0, W - 1] x [0, H - 1] if `clamp`;
+ *   d_scale_r [n] and d_ori_r [n,2] gathered from the right image's maps (or scale_value; d_ori_r and d_ori_map both
+ *   or neither) at index b H W + y' W + x' clamped to [0, n_images H W - 1], exactly as the reference does: with
+ *   clamp = 0 (eval_model's use) a keypoint projected outside keeps its outside coordinates and gathers whatever that
+ *   clamped index names.  One deliberate difference, hn_clip_patch's: the keypoint's own column 0, clamped to
+ *   [0, n_images - 1], selects the homography (the reference's .view(B, -1) agrees with it only for equal counts in
+ *   batch order).  n >= 0 (0 returns HN_OK; n > 0 needs n_images >= 1), clamp in {0, 1}. */
+int hn_warp_score(const float* d_score, const float* d_homo, int64_t n_images, int32_t height, int32_t width,
+                  int32_t border, int32_t align_corners, float* d_warped, float* d_visible, void* hip_stream);
+int hn_gt_scale_orin(const float* d_scale, float scale_value, const float* d_ori, const float* d_homo12,
+                     const float* d_homo21, int64_t n_images, int32_t height, int32_t width, float* d_gt_scale,
+                     float* d_gt_ori, void* hip_stream);
+int hn_mask_keypoints(const uint8_t* d_mask, int64_t n_images, int32_t height, int32_t width, int32_t topk,
+                      const float* d_scale_map, float scale_value, const float* d_ori_map, int64_t* d_kpts,
+                      float* d_kscale, float* d_kori, int32_t* d_counts, void* hip_stream);
+int hn_project_keypoints(const int64_t* d_kpts, int64_t n, const float* d_homo, int64_t n_images, int32_t height,
+                         int32_t width, const float* d_scale_map, float scale_value, const float* d_ori_map,
+                         int32_t clamp, int64_t* d_kpts_r, float* d_scale_r, float* d_ori_r, void* hip_stream);
+
 /* Train-mode stock HardNet (the module of hardnet/HardNet.py:275-315 in
  * model.train() as the training loop :379-441 runs it through autograd).
  *  forward : input_norm (mean / std detached), 7 x [conv -> BatchNorm2d(affine=False) with the
