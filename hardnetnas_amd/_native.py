@@ -53,10 +53,12 @@ EXPORTED = ["hn_param_count", "hn_create", "hn_workspace_bytes", "hn_forward",
             "hn_pairdist_rows", "hn_hardnet_loss", "hn_workspace_bytes_u8", "hn_forward_u8",
             "hn_hardnet_train_workspace_bytes", "hn_hardnet_train_forward", "hn_hardnet_train_backward",
             "hn_nas_train_tensor_count", "hn_nas_train_workspace_bytes", "hn_nas_train_forward",
-            "hn_nas_train_backward", "hn_hardnet_loss_train_workspace_bytes", "hn_hardnet_loss_train_forward",
-            "hn_hardnet_loss_backward", "hn_neimask_loss_workspace_bytes", "hn_neimask_loss_forward",
+            "hn_nas_train_backward", "hn_nas_train_backward_dx", "hn_hardnet_loss_train_workspace_bytes",
+            "hn_hardnet_loss_train_forward", "hn_hardnet_loss_backward",
+            "hn_neimask_loss_workspace_bytes", "hn_neimask_loss_forward",
             "hn_neimask_loss_backward", "hn_fpr95_workspace_bytes",
-            "hn_fpr95", "hn_match_workspace_bytes", "hn_match_nn2", "hn_clip_patch", "hn_workspace_bytes_kp",
+            "hn_fpr95", "hn_match_workspace_bytes", "hn_match_nn2", "hn_clip_patch", "hn_clip_patch_backward",
+            "hn_workspace_bytes_kp",
             "hn_forward_kp", "hn_det_param_count", "hn_det_create", "hn_det_workspace_bytes", "hn_det_forward",
             "hn_det_destroy", "hn_select_workspace_bytes", "hn_select_keypoints", "hn_warp_score", "hn_gt_scale_orin",
             "hn_mask_keypoints", "hn_project_keypoints", "hn_preprocess", "hn_set_profiling",
@@ -99,6 +101,7 @@ def load_library():
         lib.hn_nas_train_workspace_bytes.argtypes = [D, I64, ctypes.POINTER(S), ctypes.POINTER(S)]
         lib.hn_nas_train_forward.argtypes = [D, P, I64, PP, ctypes.c_float, P, P, P, S, P, S, P]
         lib.hn_nas_train_backward.argtypes = [D, P, P, I64, PP, P, PP, P, P, S, P, S, P]
+        lib.hn_nas_train_backward_dx.argtypes = [D, P, P, I64, PP, P, PP, P, P, P, S, P, S, P]
         lib.hn_pairdist_workspace_bytes.argtypes = [I64, ctypes.POINTER(S)]
         lib.hn_pairdist_hardneg.argtypes = [P, P, I64, I32, I32, P, P, P, S, P]
         lib.hn_pairdist_rows_workspace_bytes.argtypes = [I64, I64, ctypes.POINTER(S)]
@@ -115,6 +118,7 @@ def load_library():
         lib.hn_match_workspace_bytes.argtypes = [I64, I64, ctypes.POINTER(S)]
         lib.hn_match_nn2.argtypes = [P, I64, P, I64, I32, I32, P, P, P, S, P]
         lib.hn_clip_patch.argtypes = [P, I64, I32, I32, P, P, P, P, I64, P, P]
+        lib.hn_clip_patch_backward.argtypes = [P, P, I64, I32, I32, P, P, P, P, I64, P, P, P]
         lib.hn_workspace_bytes_kp.argtypes = [P, I64, ctypes.POINTER(S)]
         lib.hn_forward_kp.argtypes = [P, P, I64, I32, I32, P, P, P, P, I64, P, P, S, P]
         F32 = ctypes.c_float
@@ -149,6 +153,7 @@ def load_library():
                      "hn_hardnet_loss_train_forward", "hn_hardnet_loss_backward", "hn_neimask_loss_workspace_bytes",
                      "hn_neimask_loss_forward", "hn_neimask_loss_backward", "hn_match_workspace_bytes",
                      "hn_match_nn2", "hn_clip_patch", "hn_workspace_bytes_kp", "hn_forward_kp",
+                     "hn_clip_patch_backward", "hn_nas_train_backward_dx",
                      "hn_det_param_count", "hn_det_create", "hn_det_workspace_bytes", "hn_det_forward",
                      "hn_select_workspace_bytes", "hn_select_keypoints", "hn_warp_score", "hn_gt_scale_orin",
                      "hn_mask_keypoints", "hn_project_keypoints"):
@@ -675,6 +680,70 @@ def clip_patch(images: torch.Tensor, kpts: torch.Tensor, scale: torch.Tensor, or
     return out
 
 
+def clip_patch_backward(dout: torch.Tensor, images: torch.Tensor, kpts: torch.Tensor, scale: torch.Tensor,
+                        ori: Optional[torch.Tensor], ratio: torch.Tensor, want_scale: bool = True,
+                        want_ori: bool = True, out_scale: Optional[torch.Tensor] = None,
+                        out_ori: Optional[torch.Tensor] = None):
+    """Gradients of ``clip_patch`` with respect to ``scale`` [N] and ``ori`` [N,2] given the patches' gradient
+    ``dout`` fp32 [N,1,32,32], in one kernel (hn_clip_patch_backward): ``(d_scale or None, d_ori or None)``.  The
+    corners are detached as in the reference; the images, the ratio and the keypoint rows get no gradient.
+    ``want_ori`` without ``ori`` is an error.  ``out_scale`` / ``out_ori`` are optional contiguous destinations.
+    A keypoint's gradient is bit-identical call to call, alone or in any batch; the call reads nothing outside
+    ``images`` whatever the keypoint data (include/hardnet_mi355x.h)."""
+    lib = load_library()
+    im, kp, sc, orr, ra = _keypoint_args(images, kpts, scale, ori, ratio)
+    n = kp.shape[0]
+    if want_ori and orr is None:
+        raise ValueError("want_ori needs ori: without rotation there is no orientation gradient")
+    if dout.dtype != torch.float32 or dout.numel() != n * 1024 or dout.device != im.device:
+        raise ValueError(f"dout must be fp32 [{n},1,32,32] on {im.device}, got {dout.dtype} {tuple(dout.shape)} "
+                         f"on {dout.device}")
+    dout = dout.contiguous()
+
+    def dest(t, shape, what):
+        if t is None:
+            return torch.empty(shape, device=im.device, dtype=torch.float32)
+        if tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != im.device or not t.is_contiguous():
+            raise ValueError(f"{what} must be a contiguous fp32 {list(shape)} tensor on {im.device}")
+        return t
+
+    ds = dest(out_scale, (n,), "out_scale") if want_scale else None
+    do = dest(out_ori, (n, 2), "out_ori") if want_ori else None
+    stream = torch.cuda.current_stream(im.device).cuda_stream
+    with torch.cuda.device(im.device):
+        _check(lib.hn_clip_patch_backward(dout.data_ptr(), im.data_ptr(), im.shape[0], im.shape[2], im.shape[3],
+                                          kp.data_ptr(), sc.data_ptr(), orr.data_ptr() if orr is not None else None,
+                                          ra.data_ptr(), n, ds.data_ptr() if ds is not None else None,
+                                          do.data_ptr() if do is not None else None, stream),
+               "hn_clip_patch_backward")
+    return ds, do
+
+
+class ClipPatchFunction(torch.autograd.Function):
+    """``clip_patch`` with its backward to ``scale`` and ``ori`` (once differentiable; ``images``, ``kpts`` and
+    ``ratio`` get no gradient): one kernel forward, one kernel backward, which computes only the outputs that
+    ``ctx.needs_input_grad`` names.  Arguments as ``clip_patch``; ``scale`` may have any shape of N elements."""
+
+    @staticmethod
+    def forward(ctx, images, kpts, scale, ori, ratio):
+        ctx.scale_shape = scale.shape
+        flat = scale.reshape(-1)
+        ctx.has_ori = ori is not None
+        ctx.save_for_backward(images, kpts, flat, ori if ori is not None else flat.new_empty(0), ratio)
+        return clip_patch(images, kpts, flat, ori, ratio)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        images, kpts, scale, ori, ratio = ctx.saved_tensors
+        want_scale, want_ori = ctx.needs_input_grad[2], ctx.has_ori and ctx.needs_input_grad[3]
+        ds = do = None
+        if want_scale or want_ori:
+            ds, do = clip_patch_backward(dout, images, kpts, scale, ori if ctx.has_ori else None, ratio,
+                                         want_scale=want_scale, want_ori=want_ori)
+        return None, None, ds.view(ctx.scale_shape) if ds is not None else None, do, None
+
+
 class NativeDetector:
     """FDLNet's NASNet keypoint detector on the device (hn_det_create): ``blob`` is ``state_dict_blob`` of an
     ``RFDet.state_dict()`` -- features.0.{weight,bias}; per InvertedResidual banch2.0.weight, banch2.1.{weight,
@@ -1066,7 +1135,8 @@ def train_tensors(module):
 class NasTrainFunction(torch.autograd.Function):
     """model.train() forward of a hardnetNAS descriptor (``desc`` kind NAS) or of the supernet
     (kind NAS_SUPERNET, with the per-layer soft weights ``soft`` [n_layers, 17]) on the GPU
-    kernels, and its backward to every parameter (and to ``soft``) -- what autograd does over the
+    kernels, and its backward to every parameter (and to ``soft``, and to ``x`` when it requires grad:
+    hn_nas_train_backward_dx) -- what autograd does over the
     reference modules in hardnetNAS/supernet_functions/training_functions_supernet.py:88-103.
     ``tensors`` is the module's float state_dict in order (train_tensors); ``params`` are the ones
     among them that are parameters, in the same order; running buffers are updated in place."""
@@ -1122,13 +1192,17 @@ class NasTrainFunction(torch.autograd.Function):
                "hn_nas_train_workspace_bytes")
         scratch = torch.empty(sc.value, device=dout.device, dtype=torch.uint8)
         dsoft = torch.empty_like(soft_c) if ctx.has_soft else None
+        # the input gradient (conv0's data gradient through input_norm) only when the patches need one
+        din = torch.empty((ctx.b, 1, 32, 32), device=dout.device, dtype=torch.float32) \
+            if ctx.needs_input_grad[0] else None
         stream = torch.cuda.current_stream(dout.device).cuda_stream
         gp = (ctypes.c_void_p * len(gptrs))(*[g.data_ptr() if g is not None else None for g in gptrs])
         with torch.cuda.device(dout.device):
-            _check(lib.hn_nas_train_backward(ctypes.byref(ctx.desc), dout.contiguous().data_ptr(), x.data_ptr(), ctx.b,
-                                             _ptr_array(ctx.tensors),
-                                             soft_c.data_ptr() if ctx.has_soft else None, gp,
-                                             dsoft.data_ptr() if dsoft is not None else None, saved.data_ptr(),
-                                             saved.numel(), scratch.data_ptr(), scratch.numel(), stream),
-                   "hn_nas_train_backward")
-        return (None, dsoft, None, None, None, *grads)
+            _check(lib.hn_nas_train_backward_dx(ctypes.byref(ctx.desc), dout.contiguous().data_ptr(), x.data_ptr(),
+                                                ctx.b, _ptr_array(ctx.tensors),
+                                                soft_c.data_ptr() if ctx.has_soft else None, gp,
+                                                dsoft.data_ptr() if dsoft is not None else None,
+                                                din.data_ptr() if din is not None else None, saved.data_ptr(),
+                                                saved.numel(), scratch.data_ptr(), scratch.numel(), stream),
+                   "hn_nas_train_backward_dx")
+        return (din, dsoft, None, None, None, *grads)

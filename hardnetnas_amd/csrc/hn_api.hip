@@ -1468,6 +1468,21 @@ extern "C" int hn_clip_patch(const float* d_images, int64_t n_images, int32_t he
   return HN_OK;
 }
 
+extern "C" int hn_clip_patch_backward(const float* d_dpatches, const float* d_images, int64_t n_images, int32_t height,
+                                      int32_t width, const int64_t* d_kpts, const float* d_scale, const float* d_ori,
+                                      const float* d_ratio, int64_t n, float* d_dscale, float* d_dori,
+                                      void* hip_stream) {
+  if (const char* e = clip_arg_error(n_images, height, width, n)) return fail(HN_ERR_ARG, e);
+  if (d_dori && !d_ori) return fail(HN_ERR_ARG, "d_dori needs d_ori (no rotation has no orientation gradient)");
+  if (n == 0) return HN_OK;
+  if (!d_dpatches || !d_images || !d_kpts || !d_scale || !d_ratio)
+    return fail(HN_ERR_ARG, "NULL device pointer (only d_ori, d_dscale and d_dori may be NULL)");
+  if (reinterpret_cast<uintptr_t>(d_dpatches) & 15) return fail(HN_ERR_ARG, "d_dpatches must be 16-byte aligned");
+  HIPCHK(hn_launch_clip_backward(d_dpatches, d_images, n_images, height, width, d_kpts, d_scale, d_ori, d_ratio, n,
+                                 d_dscale, d_dori, static_cast<hipStream_t>(hip_stream)));
+  return HN_OK;
+}
+
 extern "C" int hn_workspace_bytes_kp(const hn_model* m, int64_t n, size_t* bytes_out) {
   int rc = hn_workspace_bytes(m, n, bytes_out);
   if (rc) return rc;
@@ -1918,6 +1933,14 @@ extern "C" int hn_nas_train_backward(const hn_arch_desc* desc, const float* d_do
                                      float* const* d_tensors, const float* d_soft, float* const* d_grads,
                                      float* d_dsoft, void* d_saved, size_t saved_bytes, void* d_scratch,
                                      size_t scratch_bytes, void* hip_stream) {
+  return hn_nas_train_backward_dx(desc, d_dout, d_in, batch, d_tensors, d_soft, d_grads, d_dsoft, nullptr, d_saved,
+                                  saved_bytes, d_scratch, scratch_bytes, hip_stream);
+}
+
+extern "C" int hn_nas_train_backward_dx(const hn_arch_desc* desc, const float* d_dout, const float* d_in,
+                                        int64_t batch, float* const* d_tensors, const float* d_soft,
+                                        float* const* d_grads, float* d_dsoft, float* d_din, void* d_saved,
+                                        size_t saved_bytes, void* d_scratch, size_t scratch_bytes, void* hip_stream) {
   int rc = nas_train_args(desc, batch, d_tensors, d_saved, saved_bytes, d_scratch, scratch_bytes, d_soft);
   if (rc) return rc;
   if (!d_dout || !d_in) return fail(HN_ERR_ARG, "NULL device pointer");
@@ -1926,7 +1949,8 @@ extern "C" int hn_nas_train_backward(const hn_arch_desc* desc, const float* d_do
     return fail(HN_ERR_ARG, "d_grads[" + std::to_string(slot) + "] is NULL: every weight slot needs a gradient buffer");
   }
   if (desc->kind == HN_KIND_NAS_SUPERNET && !d_dsoft) return fail(HN_ERR_ARG, "the supernet needs d_dsoft");
-  HIPCHK(hn_nas_train_backward_impl(*desc, d_dout, (long)batch, d_in, d_tensors, d_soft, d_grads, d_dsoft,
+  if (reinterpret_cast<uintptr_t>(d_din) & 15) return fail(HN_ERR_ARG, "d_din must be 16-byte aligned");
+  HIPCHK(hn_nas_train_backward_impl(*desc, d_dout, (long)batch, d_in, d_tensors, d_soft, d_grads, d_dsoft, d_din,
                                     static_cast<char*>(d_saved), static_cast<char*>(d_scratch),
                                     static_cast<hipStream_t>(hip_stream)));
   return HN_OK;

@@ -1,7 +1,8 @@
 // Per-sample address and weight computation of the keypoint patch extraction (hn_clip.hip), restating
 // FDLNet-master/latency/NASNet/utils/image_utils.py:11-158 (clip_patch) in fp32 in its operation order.
 // __host__ __device__ and free of HIP types, so that the same text runs in the kernel and in the host
-// program that sweeps adversarial keypoints under the sanitizers (hn_clip_host_check.cpp).
+// programs that sweep adversarial keypoints under the sanitizers (hn_clip_host_check.cpp, and
+// hn_clip_grad_host_check.cpp for the backward's functions at the end of this file).
 //
 // Bounds guarantee: whatever the keypoint data (NaN, Inf, values beyond the integer range, any batch index),
 // every pixel pair returned (p and p + 1) lies in [0, B * H * W), for B >= 1 and H, W >= 2 with B * H * W < 2^63.
@@ -116,6 +117,69 @@ HN_CLIP_HD float blend(const Sample& s, const PixelPair& top, const PixelPair& b
   const float Ia = s.hi0 ? top.hi : top.lo, Ic = s.hi1 ? top.hi : top.lo;
   const float Ib = s.hi0 ? bottom.hi : bottom.lo, Id = s.hi1 ? bottom.hi : bottom.lo;
   return s.wa * Ia + s.wb * Ib + s.wc * Ic + s.wd * Id;
+}
+
+// ---- backward (hn_clip_patch_backward): gradients to the keypoint's scale and orientation ----
+// The corners are detached (the reference's .floor().long()), so a sample's value is bilinear in (xs, ys) inside
+// its cell and its derivative is a difference of pixels weighted by the distance to the opposite edge.
+
+// One output pixel for the backward: the forward's addresses (so its bounds guarantee carries over) and the four
+// edge distances ux = x1 - xs, vx = xs - x0, uy = y1 - ys, vy = ys - y0, computed as the forward computes them.
+struct SampleGrad {
+  Sample s;
+  float ux, vx, uy, vy;
+  float gx, gy;  // the sample's grid values (col, row)
+};
+
+HN_CLIP_HD SampleGrad sample_grad(const Keypoint& k, int row, int col, int32_t H, int32_t W) {
+#pragma clang fp contract(off)
+  SampleGrad g;
+  g.s = sample(k, row, col, H, W);
+  g.gx = grid_value(col);
+  g.gy = grid_value(row);
+  const float xs = k.sc * g.gx + k.nss * g.gy + k.kx;
+  const float ys = k.ss * g.gx + k.sc * g.gy + k.ky;
+  int32_t x0, x1, y0, y1;
+  floor_pair(xs, W - 1, &x0, &x1);
+  floor_pair(ys, H - 1, &y0, &y1);
+  g.ux = (float)x1 - xs;
+  g.vx = xs - (float)x0;
+  g.uy = (float)y1 - ys;
+  g.vy = ys - (float)y0;
+  return g;
+}
+
+// Adds one sample's share of a = d out / d (s cos) and b = d out / d (s sin), d being the upstream gradient of
+// the pixel:  gX = d value / d xs = uy (Ic - Ia) + vy (Id - Ib),  gY = d value / d ys = ux (Ib - Ia) + vx (Id - Ic)
+// (pixel differences first: where clamping makes two corners one pixel the term is exactly 0), and
+// xs = (s cos) gx - (s sin) gy + kx,  ys = (s sin) gx + (s cos) gy + ky.
+HN_CLIP_HD void accumulate_grad(const SampleGrad& g, const PixelPair& top, const PixelPair& bottom, float d, float* a,
+                                float* b) {
+#pragma clang fp contract(off)
+  const float Ia = g.s.hi0 ? top.hi : top.lo, Ic = g.s.hi1 ? top.hi : top.lo;
+  const float Ib = g.s.hi0 ? bottom.hi : bottom.lo, Id = g.s.hi1 ? bottom.hi : bottom.lo;
+  const float gX = g.uy * (Ic - Ia) + g.vy * (Id - Ib);
+  const float gY = g.ux * (Ib - Ia) + g.vx * (Id - Ic);
+  *a += d * (gX * g.gx + gY * g.gy);
+  *b += d * (gY * g.gx - gX * g.gy);
+}
+
+// The chain rule from (a, b), summed over the patch, to the keypoint's scale and orientation: with
+// s = (scale / r) / 2, s cos and s sin give  d scale = (a cos + b sin) / r / 2,  d ori = (a s, b s).
+// ori null: cos = 1, sin = 0.  dscale / dori (two floats) may each be null.
+HN_CLIP_HD void keypoint_grad(const int64_t* kp, float scale, const float* ori, const float* ratio, int64_t B,
+                              float a, float b, float* dscale, float* dori) {
+#pragma clang fp contract(off)
+  int64_t bi = kp[0];
+  bi = bi < 0 ? 0 : (bi > B - 1 ? B - 1 : bi);
+  const float r = ratio[bi];
+  const float c = ori ? ori[0] : 1.0f, sn = ori ? ori[1] : 0.0f;
+  if (dscale) *dscale = ((a * c + b * sn) / r) / 2.0f;
+  if (dori) {
+    const float s = (scale / r) / 2.0f;
+    dori[0] = a * s;
+    dori[1] = b * s;
+  }
 }
 
 }  // namespace hnclip

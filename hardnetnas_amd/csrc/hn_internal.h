@@ -239,6 +239,10 @@ hipError_t hn_launch_match_nn2(const float* q, int N, const float* db, int M, in
 // ori null: no rotation.  Reads nothing outside images whatever the keypoint data (B >= 1, H, W >= 2)
 hipError_t hn_launch_clip(const float* images, int64_t B, int H, int W, const int64_t* kpts, const float* scale,
                           const float* ori, const float* ratio, int64_t n, float* out, hipStream_t st);
+// its backward to the keypoints: dscale [n] and dori [n,2] (either may be null) from dout [n,1,32,32]; same reads
+hipError_t hn_launch_clip_backward(const float* dout, const float* images, int64_t B, int H, int W,
+                                   const int64_t* kpts, const float* scale, const float* ori, const float* ratio,
+                                   int64_t n, float* dscale, float* dori, hipStream_t st);
 // FDLNet's NASNet detector (hn_det.hip): layout of the BN-folded device parameters (floats) and the launch
 namespace hndet {
 constexpr int kDetTile = 16;      // k_det_feat's output tile (one partial-statistics slot per tile)
@@ -391,7 +395,7 @@ hipError_t hn_nas_train_forward_impl(const hn_arch_desc& d, const float* in, lon
                                      hipStream_t st);
 hipError_t hn_nas_train_backward_impl(const hn_arch_desc& d, const float* dout, long B, const float* in,
                                       float* const* tensors, const float* soft, float* const* grads, float* dsoft,
-                                      char* saved, char* scratch, hipStream_t st);
+                                      float* din, char* saved, char* scratch, hipStream_t st);
 hipError_t hn_train_forward(const float* in, long B, const float* const* W, float* const* rmean, float* const* rvar,
                             float mom, float bn_eps, float in_eps, float l2_eps, float drop_p,
                             unsigned long long seed, float* out, char* saved, char* scratch, hipStream_t st);

@@ -562,6 +562,45 @@ __global__ __launch_bounds__(256) void k_head_scatter(const float* __restrict__ 
   }
 }
 
+// conv0's data gradient, the descriptor's input gradient (des.py:40-49: mean and std of input_norm detached):
+//   din[b][y][x] = inv_sd[b] sum_c sum_(dy, dx) w[c][dy][dx] g[c][b][y + 1 - dy][x + 1 - dx],  zero padding,
+// g [32][B][32][32] the gradient of conv0's output, inv_sd null (the NAS stem: no input_norm) = 1.  One workgroup
+// per patch; thread t owns row t / 8, columns 4 (t % 8) .. + 3, and reads of each channel the three rows it needs
+// as a 16-byte load (a wave: 8 full rows, 1 KiB contiguous) plus the column on either side; the 288 weights are
+// wave-uniform.  ~128 KiB read and 4 KiB written per patch, channels and taps summed in a fixed order.
+__global__ __launch_bounds__(256) void k_dgrad0(const float* __restrict__ g, const float* __restrict__ w,
+                                                const float* __restrict__ inv_sd, long B, float* __restrict__ din) {
+  const int t = threadIdx.x, y = t >> 3, x = (t & 7) * 4;
+  for (long b = blockIdx.x; b < B; b += gridDim.x) {
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+    for (int c = 0; c < 32; ++c) {
+      const float* plane = g + ((long)c * B + b) * 1024;
+      float v[3][6];  // rows y + 1, y, y - 1 (dy = 0, 1, 2), columns x - 1 .. x + 4
+#pragma unroll
+      for (int dy = 0; dy < 3; ++dy) {
+        const int yy = y + 1 - dy;
+        const bool in = yy >= 0 && yy < 32;
+        const float* r = plane + (in ? yy : 0) * 32 + x;
+        const float4 m = in ? *reinterpret_cast<const float4*>(r) : float4{0.f, 0.f, 0.f, 0.f};
+        v[dy][0] = in && x > 0 ? r[-1] : 0.f;
+        v[dy][1] = m.x, v[dy][2] = m.y, v[dy][3] = m.z, v[dy][4] = m.w;
+        v[dy][5] = in && x < 28 ? r[4] : 0.f;
+      }
+#pragma unroll
+      for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 3; ++dx) {
+          const float wv = w[c * 9 + dy * 3 + dx];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) acc[j] = fmaf(wv, v[dy][j + 2 - dx], acc[j]);
+        }
+    }
+    const float s = inv_sd ? inv_sd[b] : 1.f;
+    *reinterpret_cast<float4*>(din + b * 1024 + t * 4) = float4{acc[0] * s, acc[1] * s, acc[2] * s, acc[3] * s};
+  }
+}
+
 // every kernel launched on grid_of(n) walks its n elements in a grid-stride loop (the grid is capped)
 unsigned grid_of(long n) { return (unsigned)std::max<long>(1, std::min<long>((n + 255) / 256, 65536)); }
 
@@ -1209,7 +1248,8 @@ hipError_t nas_fwd(Ctx& c, Plan& P, const float* in, const float* soft, float* o
   return hipGetLastError();
 }
 
-hipError_t nas_bwd(Ctx& c, Plan& P, const float* in, const float* soft, const float* dout, float* dsoft) {
+hipError_t nas_bwd(Ctx& c, Plan& P, const float* in, const float* soft, const float* dout, float* dsoft,
+                   float* din) {
   const long B = P.B;
   float* g = c.s(P.g0);   // gradient of the current layer's output
   float* gx = c.s(P.g1);  // gradient of its input
@@ -1292,7 +1332,7 @@ hipError_t nas_bwd(Ctx& c, Plan& P, const float* in, const float* soft, const fl
     HCK(hipGetLastError());
     x0 = c.f(P.xn);
   } else {
-    // stem: ReLU o BN -> conv weight gradient (k_wgrad0; the input gradient is not formed)
+    // stem: ReLU o BN -> conv weight gradient (k_wgrad0)
     HCK(bn_bwd(c, g, c.f(P.x0z), c.f(P.x0r), 32, B * 1024, P.stem_bn, true, true, gx));
   }
   const long ns = wgrad0_slices(B);
@@ -1301,6 +1341,10 @@ hipError_t nas_bwd(Ctx& c, Plan& P, const float* in, const float* soft, const fl
   GemmArgs gs{nullptr, nullptr, c.G[P.stem_w], 32, 9, 0, 0, 0, 0, 0, 9, 1, 1.f, 0.f};
   hipLaunchKernelGGL(k_splitk_sum, dim3((unsigned)((32 * 9 + 63) / 64)), dim3(1024), 0, c.st, gs, (int)ns,
                      c.s(P.part));
+  // gx = the gradient of conv0's output for every kind: the input gradient, when asked for
+  if (din)
+    hipLaunchKernelGGL(k_dgrad0, dim3((unsigned)std::min<long>(B, 65536)), dim3(256), 0, c.st, gx, c.T[P.stem_w],
+                       P.fdl ? c.f(P.xsd) : nullptr, B, din);
   return hipGetLastError();
 }
 
@@ -1336,8 +1380,8 @@ hipError_t hn_nas_train_forward_impl(const hn_arch_desc& d, const float* in, lon
 
 hipError_t hn_nas_train_backward_impl(const hn_arch_desc& d, const float* dout, long B, const float* in,
                                       float* const* tensors, const float* soft, float* const* grads, float* dsoft,
-                                      char* saved, char* scratch, hipStream_t st) {
+                                      float* din, char* saved, char* scratch, hipStream_t st) {
   Plan P = make_plan(d, B);
   Ctx c{P, tensors, grads, saved, scratch, st, 0.f};
-  return nas_bwd(c, P, in, soft, dout, dsoft);
+  return nas_bwd(c, P, in, soft, dout, dsoft, din);
 }

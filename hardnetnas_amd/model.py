@@ -371,7 +371,7 @@ class HardNetNeiMask(_NativeMixin, nn.Module):
         y = self._dispatch_native(input)
         if y is not None:
             return y
-        walk = _nas_train_native_eligible(self, input, A.FDL_LAYERS, A.FDL_LAYERS)
+        walk = _nas_train_native_eligible(self, input, A.FDL_LAYERS, A.FDL_LAYERS, input_grad=True)
         if walk is not None:
             return _nas_train_native_forward(self, input, None, walk)
         x_features = self.features(self.input_norm(input))
@@ -443,9 +443,11 @@ class HardNetNAS(_NativeMixin, nn.Module):
         return self.load_state_dict(out, strict=strict)
 
 
-def _nas_train_native_eligible(module: nn.Module, x: torch.Tensor, layers, expect=A.SEARCH_SPACE2):
+def _nas_train_native_eligible(module: nn.Module, x: torch.Tensor, layers, expect=A.SEARCH_SPACE2,
+                               input_grad: bool = False):
     """model.train() of HardNetNAS / HardNetNASSupernet / HardNetNeiMask on a HIP fp32
-    [B>=2,1,32,32] batch that needs no input gradient, with the reference's BatchNorm setup (one
+    [B>=2,1,32,32] batch that needs no input gradient (or, with ``input_grad``, may need one: HardNetNeiMask, whose
+    patches come from clip_patch with the detector's orientation), with the reference's BatchNorm setup (one
     momentum, running statistics tracked, eps 1e-5) and every parameter / buffer fp32 contiguous on
     x's device, runs hn_nas_train_* (SURVEY 8(f) row 4).  Anything else runs the module's torch
     layers (returns None).  Eligible: returns (bns, tensors) -- the BatchNorms, and the float state_dict
@@ -454,7 +456,7 @@ def _nas_train_native_eligible(module: nn.Module, x: torch.Tensor, layers, expec
     that checks them (the supernet has ~1,400 modules: one walk instead of five per forward)."""
     if not (getattr(module, "native_train", True) and module.training and x.is_cuda
             and x.dtype == torch.float32 and x.dim() == 4 and tuple(x.shape[1:]) == (1, 32, 32)
-            and x.shape[0] >= 2 and not (torch.is_grad_enabled() and x.requires_grad)
+            and x.shape[0] >= 2 and (input_grad or not (torch.is_grad_enabled() and x.requires_grad))
             and list(layers) == list(expect)):
         return None
     return _nas_train_walk(module, x.device)

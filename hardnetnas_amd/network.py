@@ -283,9 +283,11 @@ def _clip_patch_matmul(kpts_byxc, kpts_scale, kpts_ori, im_info, images, PSIZE):
 
 
 def _pair_patches(kpts_byxc, kpts_scale, kpts_ori, im_info, images, PSIZE):
-    """The patches of ``pair``: ``hn_clip_patch`` where ``patches.clip_patch`` would run it, else the reference's
-    operation order (``_clip_patch_matmul``)."""
-    if _patches._native_ok(kpts_byxc, kpts_scale, kpts_ori, im_info, images, PSIZE):
+    """The patches of ``pair``: ``hn_clip_patch`` where ``patches.clip_patch`` would run it -- alone, or under autograd
+    on the keypoints' scale / orientation with ``hn_clip_patch_backward`` behind it -- else the reference's operation
+    order (``_clip_patch_matmul``)."""
+    if (_patches._native_ok(kpts_byxc, kpts_scale, kpts_ori, im_info, images, PSIZE)
+            or _patches._native_grad_ok(kpts_byxc, kpts_scale, kpts_ori, im_info, images, PSIZE)):
         return clip_patch(kpts_byxc, kpts_scale, kpts_ori, im_info, images, PSIZE=PSIZE)
     return _clip_patch_matmul(kpts_byxc, kpts_scale, kpts_ori, im_info, images, PSIZE)
 

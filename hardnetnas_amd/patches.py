@@ -9,9 +9,12 @@ detector's keypoints and the descriptor in ``Network.inference`` (model/network.
 
 The reference runs some 60 small kernels and twenty [N * PSIZE^2] temporaries; here fp32 HIP ``images``
 [B,1,H,W] with int64 keypoints on the same device and PSIZE == 32 go through ``_native.clip_patch`` (one kernel,
-hn_clip.hip).  Everything else -- CPU tensors, fp64, another PSIZE, or autograd recording on ``images`` /
-``kpts_scale`` / ``kpts_ori`` -- runs the torch formulation below in the dtype of ``images``; in fp64 (grid
-values still the fp32 ``linspace`` values) it is the ground truth of the tests.
+hn_clip.hip).  With autograd recording on fp32 ``kpts_scale`` / ``kpts_ori`` (the training step: both come from
+the detector's maps) the same inputs go through ``_native.ClipPatchFunction``: that kernel forward and
+``hn_clip_patch_backward`` backward, gradients to scale and orientation only, once differentiable.  Everything
+else -- CPU tensors, fp64, another PSIZE, or ``images`` / ``im_info`` requiring grad -- runs the torch formulation
+below in the dtype of ``images``; in fp64 (grid values still the fp32 ``linspace`` values) it is the ground truth
+of the tests.
 
 ``describe_keypoints`` is ``des(clip_patch(..., 32))`` in one call; with one of this package's descriptor
 modules in eval mode on a HIP device it runs ``NativeModel.forward_keypoints`` and the patches never leave the
@@ -36,14 +39,28 @@ def _records_grad(*ts) -> bool:
     return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts)
 
 
-def _native_ok(kpts_byxc, kpts_scale, kpts_ori, im_info, images, PSIZE) -> bool:
+def _native_shapes_ok(kpts_byxc, kpts_scale, kpts_ori, im_info, images, PSIZE) -> bool:
     dev = images.device
     return (PSIZE == NATIVE_PSIZE and images.is_cuda and images.dtype == torch.float32 and images.dim() == 4
             and images.shape[1] == 1 and kpts_byxc.dtype == torch.int64 and kpts_byxc.device == dev
             and kpts_byxc.dim() == 2 and kpts_byxc.shape[1] == 4
             and kpts_scale.device == dev and im_info.device == dev
-            and (kpts_ori is None or kpts_ori.device == dev)
+            and (kpts_ori is None or kpts_ori.device == dev))
+
+
+def _native_ok(kpts_byxc, kpts_scale, kpts_ori, im_info, images, PSIZE) -> bool:
+    """The kernel alone: no autograd graph to record."""
+    return (_native_shapes_ok(kpts_byxc, kpts_scale, kpts_ori, im_info, images, PSIZE)
             and not _records_grad(images, kpts_scale, kpts_ori))
+
+
+def _native_grad_ok(kpts_byxc, kpts_scale, kpts_ori, im_info, images, PSIZE) -> bool:
+    """The kernel with its backward (``_native.ClipPatchFunction``): ``_native_ok``'s conditions with autograd
+    recording on the fp32 ``kpts_scale`` and / or ``kpts_ori`` -- the training step, where the detector's maps give
+    both -- while ``images`` and ``im_info``, which the kernel does not differentiate, require no grad."""
+    return (_native_shapes_ok(kpts_byxc, kpts_scale, kpts_ori, im_info, images, PSIZE)
+            and _records_grad(kpts_scale, kpts_ori) and not _records_grad(images, im_info)
+            and kpts_scale.dtype == torch.float32 and (kpts_ori is None or kpts_ori.dtype == torch.float32))
 
 
 def _native_args(kpts_scale, kpts_ori, im_info):
@@ -102,6 +119,10 @@ def clip_patch(kpts_byxc, kpts_scale, kpts_ori, im_info, images, PSIZE):
     if _native_ok(kpts_byxc, kpts_scale, kpts_ori, im_info, images, PSIZE):
         from . import _native
         return _native.clip_patch(images.detach(), kpts_byxc, *_native_args(kpts_scale, kpts_ori, im_info))
+    if _native_grad_ok(kpts_byxc, kpts_scale, kpts_ori, im_info, images, PSIZE):
+        from . import _native
+        return _native.ClipPatchFunction.apply(images.detach(), kpts_byxc, kpts_scale, kpts_ori,
+                                               im_info.detach()[:, 0].float().contiguous())
     return _clip_patch_torch(kpts_byxc, kpts_scale, kpts_ori, im_info, images, PSIZE)
 
 

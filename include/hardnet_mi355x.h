@@ -301,6 +301,28 @@ int hn_clip_patch(const float* d_images, int64_t n_images, int32_t height, int32
                   const float* d_scale, const float* d_ori, const float* d_ratio, int64_t n, float* d_patches,
                   void* hip_stream);
 
+/* Backward of hn_clip_patch to the keypoints' scale and orientation: d_dscale [n] and d_dori [n,2] from the
+ * patches' gradient d_dpatches [n,1,32,32] (16-byte aligned); every other argument as in the forward call.  Not
+ * differentiated: the images, the ratio and the integer keypoint rows.  Either output may be NULL (not computed);
+ * d_dori != NULL without d_ori is HN_ERR_ARG.
+ * Mathematics: the corners are detached (the reference's .floor().long()), so inside its cell a sample is bilinear
+ * in (xs, ys).  With d the sample's upstream gradient, g[col], g[row] its grid values and the clamped corners of
+ * the forward:
+ *   gX = (y1 - ys)(Ic - Ia) + (ys - y0)(Id - Ib);   gY = (x1 - xs)(Ib - Ia) + (xs - x0)(Id - Ic)
+ *   (pixel differences first: where clamping makes two corners one pixel the term is exactly 0);
+ *   a = sum d (gX g[col] + gY g[row]) = d/d(s cos);   b = sum d (gY g[col] - gX g[row]) = d/d(s sin);
+ *   d_dscale = (a cos + b sin) / r / 2;   d_dori = (a s, b s),  s = (scale / r) / 2;   no rotation: cos 1, sin 0.
+ * fp32 without fused multiply-add; the 1,024 terms of a keypoint are summed in a fixed order by one workgroup (no
+ * atomics), so a keypoint's gradient is bit-identical call to call, alone or inside any batch.
+ * Bounds guarantee: the forward's -- the sample addresses are computed by the same code, and the call reads no
+ * byte outside d_images whatever the keypoint data.  The gradient of a keypoint with non-finite data is
+ * unspecified; every other keypoint's gradient is unaffected.
+ * Caller's stream, no allocation or synchronisation inside, capturable; the argument checks are hn_clip_patch's
+ * and run before the GPU is touched (n == 0 returns HN_OK). */
+int hn_clip_patch_backward(const float* d_dpatches, const float* d_images, int64_t n_images, int32_t height,
+                           int32_t width, const int64_t* d_kpts, const float* d_scale, const float* d_ori,
+                           const float* d_ratio, int64_t n, float* d_dscale, float* d_dori, void* hip_stream);
+
 /* Descriptors of keypoints: hn_clip_patch into the workspace tail, a chunk of min(n, chunk) keypoints at a
  * time, then the model's forward on the chunk.  Equals hn_clip_patch followed by hn_forward bit for bit, for
  * every model kind; d_out [n,128] fp32.  Workspace: hn_workspace_bytes_kp = hn_workspace_bytes + min(n, chunk)
@@ -483,7 +505,11 @@ int hn_hardnet_train_backward(const float* d_dout, int64_t batch, const float* c
  *           unbiased variance).  d_in [B,1,32,32] fp32 (NAS: no input_norm, the NAS loaders normalise;
  *           FDL: input_norm in the forward).
  * backward: d_dout [B,128] -> d_grads (every conv weight, BN weight / bias and SE weight / bias,
- *           overwritten); no input gradient.
+ *           overwritten).  hn_nas_train_backward forms no input gradient; hn_nas_train_backward_dx is the same
+ *           call with d_din [B,1,32,32] (16-byte aligned; NULL: none, then the two calls are identical), which
+ *           receives d loss / d d_in for every kind: conv0's data gradient (zero padding, fp32 FMA) times, for
+ *           the FDL kinds, the saved 1 / (std + eps) of input_norm, whose mean and std are detached (des.py:40-49).
+ *           Every other result is bit-identical with or without d_din; the workspace sizes are the same.
  * d_tensors: host array of hn_nas_train_tensor_count() device pointers, one per float tensor of the
  * module's state_dict in order (num_batches_tracked and the supernet's `thetas` left out): conv
  * weights, BN weight, bias, running_mean, running_var (updated in place), SE weights / biases.
@@ -501,6 +527,10 @@ int hn_nas_train_backward(const hn_arch_desc* desc, const float* d_dout, const f
                           float* const* d_tensors, const float* d_soft, float* const* d_grads, float* d_dsoft,
                           void* d_saved, size_t saved_bytes, void* d_scratch, size_t scratch_bytes,
                           void* hip_stream);
+int hn_nas_train_backward_dx(const hn_arch_desc* desc, const float* d_dout, const float* d_in, int64_t batch,
+                             float* const* d_tensors, const float* d_soft, float* const* d_grads, float* d_dsoft,
+                             float* d_din, void* d_saved, size_t saved_bytes, void* d_scratch, size_t scratch_bytes,
+                             void* hip_stream);
 
 /* Per-stage timing (profiling aid used by bench.py): when enabled, hn_forward records a
  * hipEvent pair around every kernel launch on the caller's stream.  hn_stage_times
