@@ -60,7 +60,8 @@ EXPORTED = ["hn_param_count", "hn_create", "hn_workspace_bytes", "hn_forward",
             "hn_fpr95", "hn_match_workspace_bytes", "hn_match_nn2", "hn_clip_patch", "hn_clip_patch_backward",
             "hn_workspace_bytes_kp",
             "hn_forward_kp", "hn_det_param_count", "hn_det_create", "hn_det_workspace_bytes", "hn_det_forward",
-            "hn_det_destroy", "hn_select_workspace_bytes", "hn_select_keypoints", "hn_warp_score", "hn_gt_scale_orin",
+            "hn_det_destroy", "hn_det_train_workspace_bytes", "hn_det_train_forward", "hn_det_train_backward",
+            "hn_select_workspace_bytes", "hn_select_keypoints", "hn_warp_score", "hn_gt_scale_orin",
             "hn_mask_keypoints", "hn_project_keypoints", "hn_preprocess", "hn_set_profiling",
             "hn_stage_times", "hn_destroy", "hn_last_error", "hn_abi_version"]
 
@@ -128,6 +129,9 @@ def load_library():
         lib.hn_det_forward.argtypes = [P, P, I64, I32, I32, P, P, P, S, P]
         lib.hn_det_destroy.argtypes = [P]
         lib.hn_det_destroy.restype = None
+        lib.hn_det_train_workspace_bytes.argtypes = [I64, I32, I32, ctypes.POINTER(S), ctypes.POINTER(S)]
+        lib.hn_det_train_forward.argtypes = [P, I64, I32, I32, PP, F32, F32, F32, P, P, P, S, P, S, P]
+        lib.hn_det_train_backward.argtypes = [P, P, P, I64, I32, I32, PP, PP, P, S, P, S, P]
         lib.hn_select_workspace_bytes.argtypes = [I64, I32, I32, I32, ctypes.POINTER(S)]
         lib.hn_select_keypoints.argtypes = [P, I64, I32, I32, I32, F32, I32, I32, I32, F32, P, F32, P, P, P, P, P, P, P,
                                             P, S, P]
@@ -156,7 +160,8 @@ def load_library():
                      "hn_clip_patch_backward", "hn_nas_train_backward_dx",
                      "hn_det_param_count", "hn_det_create", "hn_det_workspace_bytes", "hn_det_forward",
                      "hn_select_workspace_bytes", "hn_select_keypoints", "hn_warp_score", "hn_gt_scale_orin",
-                     "hn_mask_keypoints", "hn_project_keypoints"):
+                     "hn_mask_keypoints", "hn_project_keypoints", "hn_det_train_workspace_bytes",
+                     "hn_det_train_forward", "hn_det_train_backward"):
             getattr(lib, name).restype = ctypes.c_int
         if lib.hn_abi_version() != ABI_VERSION:
             raise RuntimeError(f"{path}: ABI version {lib.hn_abi_version()}, expected {ABI_VERSION}; rebuild it")
@@ -810,6 +815,133 @@ class NativeDetector:
             self.close()
         except Exception:
             pass
+
+
+# ----------------------------------------------------------------------------------
+# the detector in train() (hn_det_train_*)
+# ----------------------------------------------------------------------------------
+DET_TRAIN_TENSORS = 40  # HN_DET_TRAIN_TENSORS
+
+
+def det_train_workspace_bytes(n_images: int, height: int, width: int):
+    """(saved, scratch) bytes of hn_det_train_forward / _backward."""
+    sv, sc = ctypes.c_size_t(), ctypes.c_size_t()
+    _check(load_library().hn_det_train_workspace_bytes(n_images, height, width, ctypes.byref(sv), ctypes.byref(sc)),
+           "hn_det_train_workspace_bytes")
+    return sv.value, sc.value
+
+
+def det_train_tensors(det):
+    """The 40 float state_dict tensors of an ``RFDet`` the train ABI walks, in order (num_batches_tracked left out)."""
+    return [v for k, v in det.state_dict(keep_vars=True).items() if not k.endswith("num_batches_tracked")]
+
+
+def _det_train_check(images, tensors):
+    if (not images.is_cuda or images.dtype != torch.float32 or images.dim() != 4 or images.shape[1] != 1
+            or not images.is_contiguous()):
+        raise ValueError(f"expected contiguous fp32 [B,1,H,W] images on a HIP device, got {images.dtype} "
+                         f"{tuple(images.shape)} on {images.device}")
+    if len(tensors) != DET_TRAIN_TENSORS:
+        raise ValueError(f"the detector has {DET_TRAIN_TENSORS} float state_dict tensors, got {len(tensors)}")
+    for i, t in enumerate(tensors):
+        if t.device != images.device or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"tensor {i} must be contiguous fp32 on {images.device}")
+
+
+def _det_ws(t, need, dev, what):
+    if t is None:
+        return torch.empty(max(need, 16), device=dev, dtype=torch.uint8)
+    if t.dtype != torch.uint8 or t.device != dev or not t.is_contiguous() or t.numel() < need:
+        raise ValueError(f"{what} must be a contiguous uint8 tensor of at least {need} bytes on {dev}")
+    return t
+
+
+def det_train_forward(images, tensors, bn_eps: float, in_eps: float, momentum: float, score=None, ori=None,
+                      saved=None, scratch=None):
+    """``hn_det_train_forward``: images fp32 [B,1,H,W] -> (score [B,H,W], ori [B,H,W,2], saved).  ``tensors`` are the
+    module's 40 float state tensors (det_train_tensors); the running statistics among them are updated in place.
+    ``saved`` is what det_train_backward reads; outputs and workspaces may be passed in."""
+    lib = load_library()
+    _det_train_check(images, tensors)
+    dev = images.device
+    b, _, h, w = images.shape
+    n_sv, n_sc = det_train_workspace_bytes(b, h, w)
+    score = torch.empty((b, h, w), device=dev, dtype=torch.float32) if score is None else score
+    ori = torch.empty((b, h, w, 2), device=dev, dtype=torch.float32) if ori is None else ori
+    for t, shp in ((score, (b, h, w)), (ori, (b, h, w, 2))):
+        if tuple(t.shape) != shp or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"outputs must be contiguous fp32 {shp} tensors on {dev}")
+    saved = _det_ws(saved, n_sv, dev, "saved")
+    scratch = _det_ws(scratch, n_sc, dev, "scratch")
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        _check(lib.hn_det_train_forward(images.data_ptr(), b, h, w, _ptr_array(tensors), float(bn_eps), float(in_eps),
+                                        float(momentum), score.data_ptr(), ori.data_ptr(), saved.data_ptr(),
+                                        saved.numel(), scratch.data_ptr(), scratch.numel(), stream),
+               "hn_det_train_forward")
+    return score, ori, saved
+
+
+def det_train_backward(dscore, dori, images, tensors, grads, saved, scratch=None):
+    """``hn_det_train_backward``: the upstream gradients (either may be None: zero) -> ``grads``, a list parallel to
+    ``tensors`` with a buffer for every parameter and None for the running statistics."""
+    lib = load_library()
+    _det_train_check(images, tensors)
+    dev = images.device
+    b, _, h, w = images.shape
+    _, n_sc = det_train_workspace_bytes(b, h, w)
+    scratch = _det_ws(scratch, n_sc, dev, "scratch")
+    for t, shp in ((dscore, (b, h, w)), (dori, (b, h, w, 2))):
+        if t is not None and (tuple(t.shape) != shp or t.dtype != torch.float32 or t.device != dev
+                              or not t.is_contiguous()):
+            raise ValueError(f"upstream gradients must be contiguous fp32 {shp} tensors on {dev}")
+    for t, g in zip(tensors, grads):
+        if g is not None and (g.shape != t.shape or g.dtype != torch.float32 or g.device != dev
+                              or not g.is_contiguous()):
+            raise ValueError("every gradient buffer must be a contiguous fp32 tensor of its parameter's shape")
+    gp = (ctypes.c_void_p * len(grads))(*[g.data_ptr() if g is not None else None for g in grads])
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        _check(lib.hn_det_train_backward(dscore.data_ptr() if dscore is not None else None,
+                                         dori.data_ptr() if dori is not None else None, images.data_ptr(), b, h, w,
+                                         _ptr_array(tensors), gp, saved.data_ptr(), saved.numel(),
+                                         scratch.data_ptr(), scratch.numel(), stream), "hn_det_train_backward")
+    return grads
+
+
+class DetTrainFunction(torch.autograd.Function):
+    """``RFDet.forward`` with the module in train() on the GPU kernels (BatchNorm on the batch's statistics, running
+    statistics updated in place) and its backward to every parameter -- what autograd does over the reference module
+    in FDLNet's training step.  ``tensors`` is the module's float state in order (det_train_tensors), ``bn`` its
+    BatchNorm modules (num_batches_tracked incremented) and ``params`` the tensors among ``tensors`` that require
+    grad, in the same order.  Returns (score [B,H,W,1], ori [B,H,W,2]); the images get no gradient.  Each call keeps
+    its own "saved" workspace as a tensor saved for backward."""
+
+    @staticmethod
+    def forward(ctx, images, tensors, bn, bn_eps, in_eps, momentum, *params):
+        images = _aligned16(images)  # a batch cut out of a larger one may start at any float
+        score, ori, saved = det_train_forward(images, tensors, bn_eps, in_eps, momentum)
+        torch._foreach_add_([m.num_batches_tracked for m in bn], 1)
+        ctx.tensors = tensors
+        # per slot: 1 = a parameter whose gradient is returned, 2 = a frozen parameter (the kernels still write
+        # its gradient: it gets a throwaway buffer), 0 = a buffer (running statistics)
+        ctx.slot = [1 if t.requires_grad else 2 if isinstance(t, torch.nn.Parameter) else 0 for t in tensors]
+        ctx.set_materialize_grads(False)  # an unused output's gradient stays None: the kernels' NULL path
+        ctx.save_for_backward(saved, images, *params)
+        return score.unsqueeze(-1), ori
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dscore, dori):
+        saved, images, *params = ctx.saved_tensors
+        # one allocation for every parameter's gradient, handed out as views of the parameters' shapes
+        flat = torch.empty(sum(p.numel() for p in params), device=images.device, dtype=torch.float32)
+        grads = [g.view(p.shape) for g, p in zip(flat.split([p.numel() for p in params]), params)]
+        it = iter(grads)
+        bufs = [next(it) if k == 1 else torch.empty_like(t) if k == 2 else None for k, t in zip(ctx.slot, ctx.tensors)]
+        det_train_backward(_aligned16(dscore).squeeze(-1) if dscore is not None else None,
+                           _aligned16(dori) if dori is not None else None, images, ctx.tensors, bufs, saved)
+        return (None, None, None, None, None, None, *grads)
 
 
 def select_workspace_bytes(n_images: int, height: int, width: int, topk: int) -> int:

@@ -1642,6 +1642,80 @@ extern "C" int hn_det_forward(hn_detector* d, const float* d_images, int64_t n_i
   return HN_OK;
 }
 
+// the detector in train() (hn_det_train.hip): what the three entry points check about the images; null = fine
+static const char* det_train_arg_error(int64_t n_images, int32_t height, int32_t width) {
+  if (n_images < 1) return "n_images must be >= 1";
+  if (height < 1 || width < 1) return "height and width must be >= 1";
+  if ((int64_t)height * width > INT32_MAX) return "height * width must be below 2^31";
+  if (n_images > (1 << 24)) return "n_images must be at most 2^24";
+  if (n_images * height * width < 2) return "n_images * height * width must be >= 2 (the unbiased batch variance)";
+  return nullptr;
+}
+
+extern "C" int hn_det_train_workspace_bytes(int64_t n_images, int32_t height, int32_t width, size_t* saved_bytes_out,
+                                            size_t* scratch_bytes_out) {
+  if (!saved_bytes_out || !scratch_bytes_out) return fail(HN_ERR_ARG, "NULL size pointer");
+  if (const char* e = det_train_arg_error(n_images, height, width)) return fail(HN_ERR_ARG, e);
+  hn_det_train_plan(n_images, height, width, saved_bytes_out, scratch_bytes_out);
+  return HN_OK;
+}
+
+static int det_train_args(int64_t n_images, int32_t height, int32_t width, const float* images,
+                          float* const* tensors, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes) {
+  if (const char* e = det_train_arg_error(n_images, height, width)) return fail(HN_ERR_ARG, e);
+  if (!images || !saved || !scratch) return fail(HN_ERR_ARG, "NULL device pointer");
+  if ((reinterpret_cast<uintptr_t>(images) | reinterpret_cast<uintptr_t>(saved) |
+       reinterpret_cast<uintptr_t>(scratch)) & 15)
+    return fail(HN_ERR_ARG, "d_images, d_saved and d_scratch must be 16-byte aligned");
+  size_t need_sv = 0, need_sc = 0;
+  hn_det_train_plan(n_images, height, width, &need_sv, &need_sc);
+  if (saved_bytes < need_sv)
+    return fail(HN_ERR_WORKSPACE, "saved workspace too small: need " + std::to_string(need_sv) + " bytes");
+  if (scratch_bytes < need_sc)
+    return fail(HN_ERR_WORKSPACE, "scratch workspace too small: need " + std::to_string(need_sc) + " bytes");
+  if (!tensors) return fail(HN_ERR_ARG, "NULL tensor pointer array");
+  for (int i = 0; i < HN_DET_TRAIN_TENSORS; ++i)
+    if (!tensors[i]) return fail(HN_ERR_ARG, "NULL tensor pointer " + std::to_string(i));
+  return HN_OK;
+}
+
+extern "C" int hn_det_train_forward(const float* d_images, int64_t n_images, int32_t height, int32_t width,
+                                    float* const* d_tensors, float bn_eps, float in_eps, float momentum,
+                                    float* d_score, float* d_ori, void* d_saved, size_t saved_bytes, void* d_scratch,
+                                    size_t scratch_bytes, void* hip_stream) {
+  int rc = det_train_args(n_images, height, width, d_images, d_tensors, d_saved, saved_bytes, d_scratch,
+                          scratch_bytes);
+  if (rc) return rc;
+  if (!(bn_eps > 0.f) || !(in_eps > 0.f)) return fail(HN_ERR_ARG, "bn_eps and in_eps must be > 0");
+  if (!(momentum >= 0.f && momentum <= 1.f)) return fail(HN_ERR_ARG, "momentum must be in 0 .. 1");
+  if (!d_score || !d_ori) return fail(HN_ERR_ARG, "NULL device pointer");
+  if ((reinterpret_cast<uintptr_t>(d_score) | reinterpret_cast<uintptr_t>(d_ori)) & 15)
+    return fail(HN_ERR_ARG, "d_score and d_ori must be 16-byte aligned");
+  HIPCHK(hn_det_train_forward_impl(d_images, n_images, height, width, d_tensors, bn_eps, in_eps, momentum, d_score,
+                                   d_ori, static_cast<char*>(d_saved), static_cast<char*>(d_scratch),
+                                   static_cast<hipStream_t>(hip_stream)));
+  return HN_OK;
+}
+
+extern "C" int hn_det_train_backward(const float* d_dscore, const float* d_dori, const float* d_images,
+                                     int64_t n_images, int32_t height, int32_t width, float* const* d_tensors,
+                                     float* const* d_grads, void* d_saved, size_t saved_bytes, void* d_scratch,
+                                     size_t scratch_bytes, void* hip_stream) {
+  int rc = det_train_args(n_images, height, width, d_images, d_tensors, d_saved, saved_bytes, d_scratch,
+                          scratch_bytes);
+  if (rc) return rc;
+  if ((reinterpret_cast<uintptr_t>(d_dscore) | reinterpret_cast<uintptr_t>(d_dori)) & 15)
+    return fail(HN_ERR_ARG, "d_dscore and d_dori must be 16-byte aligned");
+  if (!d_grads) return fail(HN_ERR_ARG, "NULL gradient pointer array");
+  for (int i = 0; i < HN_DET_TRAIN_TENSORS; ++i)
+    if (hn_det_train_is_param(i) && !d_grads[i])
+      return fail(HN_ERR_ARG, "d_grads[" + std::to_string(i) + "] is NULL: every parameter slot needs a gradient buffer");
+  HIPCHK(hn_det_train_backward_impl(d_dscore, d_dori, d_images, n_images, height, width, d_tensors, d_grads,
+                                    static_cast<char*>(d_saved), static_cast<char*>(d_scratch),
+                                    static_cast<hipStream_t>(hip_stream)));
+  return HN_OK;
+}
+
 // what hn_select_workspace_bytes and hn_select_keypoints check about the map and K; null = fine
 static const char* select_arg_error(int64_t n_images, int32_t height, int32_t width, int32_t topk) {
   if (n_images < 0) return "n_images must be >= 0";

@@ -268,6 +268,15 @@ int64_t hn_det_parts(int H, int W);  // partial-statistics slots (k_det_feat wor
 size_t hn_det_ws_bytes(int64_t B, int H, int W);
 hipError_t hn_launch_det(const float* params, float in_eps, const float* images, int64_t B, int H, int W, float* score,
                          float* ori, void* ws, hipStream_t st);
+// the detector in train() (hn_det_train.hip): T / G are host arrays of 40 device pointers, RFDet.state_dict() order
+void hn_det_train_plan(int64_t n, int H, int W, size_t* saved, size_t* scratch);
+bool hn_det_train_is_param(int slot);  // false for the running statistics' slots
+hipError_t hn_det_train_forward_impl(const float* images, int64_t n, int H, int W, float* const* T, float bn_eps,
+                                     float in_eps, float momentum, float* score, float* ori, char* saved,
+                                     char* scratch, hipStream_t st);
+hipError_t hn_det_train_backward_impl(const float* dscore, const float* dori, const float* images, int64_t n, int H,
+                                      int W, float* const* T, float* const* G, char* saved, char* scratch,
+                                      hipStream_t st);
 // keypoint selection (hn_select.hip); taps: the gauss_ksize^2 blur weights, row-major (host memory)
 struct HnSelectArgs {
   const float* score;

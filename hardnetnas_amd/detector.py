@@ -6,9 +6,11 @@
 ``RFDet`` is a drop-in for the NASNet variant's detector (model/det.py): the reference's constructor arguments,
 attributes and ``state_dict`` keys, so a reference checkpoint loads with ``strict=True``.  In eval mode on HIP fp32
 ``[B,1,H,W]`` images with no autograd graph to record, ``forward`` runs ``hn_det_forward`` (two kernels, hn_det.hip)
-and ``process`` / ``detect`` run ``hn_select_keypoints`` (hn_select.hip).  Everywhere else -- CPU tensors, fp64,
-train mode, autograd -- the torch layers below run; they restate the reference formulas operation by operation and
-in fp64 are the ground truth of the tests.
+and ``process`` / ``detect`` run ``hn_select_keypoints`` (hn_select.hip).  In train mode under autograd, on HIP fp32
+images that need no gradient, ``forward`` runs ``hn_det_train_forward`` and records a ``DetTrainFunction`` node whose
+backward is ``hn_det_train_backward`` (hn_det_train.hip).  Everywhere else -- CPU tensors, fp64, train mode under
+``no_grad``, eval mode under autograd -- the torch layers below run; they restate the reference formulas operation
+by operation and in fp64 are the ground truth of the tests.
 
 ``select_keypoints_torch`` restates the selection with the C ABI's tie rule: both top-K steps order pixels by
 (value descending, flat index ascending) -- a stable descending sort -- where the reference leaves ties to
@@ -190,6 +192,36 @@ class RFDet(nn.Module):
                 and not (torch.is_grad_enabled() and (photos.requires_grad
                                                       or any(p.requires_grad for p in self.parameters()))))
 
+    def _native_train_ok(self, photos) -> bool:
+        """train() under autograd on HIP fp32 images that need no gradient: ``forward`` runs ``hn_det_train_forward``
+        and records a ``DetTrainFunction`` node (every BatchNorm tracking running statistics with one float momentum
+        and one eps, which the C ABI takes once)."""
+        if not (self.training and torch.is_grad_enabled() and photos.is_cuda and photos.dtype == torch.float32
+                and photos.dim() == 4 and photos.shape[1] == 1 and photos.is_contiguous()
+                and photos.numel() >= 2 and not photos.requires_grad):
+            return False
+        tensors = [*self.parameters(), *self.buffers()]
+        if not (all(t.device == photos.device and (t.dtype == torch.float32 or not t.is_floating_point())
+                    for t in tensors) and any(p.requires_grad for p in self.parameters())):
+            return False
+        bns = self._batchnorms()
+        return (all(m.track_running_stats and isinstance(m.momentum, float) and m.running_mean is not None
+                    for m in bns)
+                and len({m.momentum for m in bns}) == 1 and len({m.eps for m in bns}) == 1
+                and self.insnorm.eps == self.insnorm_ori.eps and self.insnorm.affine and self.insnorm_ori.affine
+                and not self.insnorm.track_running_stats and not self.insnorm_ori.track_running_stats)
+
+    def _batchnorms(self):
+        return [m for m in self.features.modules() if isinstance(m, nn.BatchNorm2d)]
+
+    def forward_train_maps(self, photos):
+        """(score [B,H,W,1], ori [B,H,W,2]) of the native train-mode forward, with its autograd node."""
+        from . import _native
+        tensors = _native.det_train_tensors(self)
+        bns = self._batchnorms()
+        return _native.DetTrainFunction.apply(photos, tensors, bns, bns[0].eps, self.insnorm.eps, bns[0].momentum,
+                                              *[t for t in tensors if t.requires_grad])
+
     def native_detector(self, device):
         """The NativeDetector of the current weights on ``device`` (rebuilt when a tensor of the state changes)."""
         from . import _native
@@ -209,6 +241,11 @@ class RFDet(nn.Module):
 
     # ---- the reference's methods -------------------------------------------------------------------------------
     def forward(self, photos):
+        if self._native_train_ok(photos):
+            # the scale map is the constant 32 with no graph: in the reference its gradient is exactly zero (the two
+            # paths through input - max in soft_max_and_argmax_1d cancel)
+            score, ori = self.forward_train_maps(photos)
+            return score, torch.full((), float(self.scale_list[0]), device=score.device).expand_as(score), ori
         if self._native_ok(photos):
             score, ori = self.forward_maps(photos)
             score = score.unsqueeze(-1)

@@ -366,6 +366,40 @@ int hn_det_forward(hn_detector* d, const float* d_images, int64_t n_images, int3
                    float* d_score, float* d_ori, void* d_workspace, size_t workspace_bytes, void* hip_stream);
 void hn_det_destroy(hn_detector* d);
 
+/* The same detector in train() and its backward: what autograd does over RFDet in FDLNet's training step
+ * (train.py:310-336 calls det(im1), det(im2) with model.train()).  Shaped like hn_nas_train_*: no handle and no
+ * host blob -- the weights change every step and are read where the optimiser left them.
+ * d_tensors: host array of HN_DET_TRAIN_TENSORS device pointers, the float tensors of RFDet.state_dict() in its
+ *   order (the order hn_det_create documents; num_batches_tracked left out, the caller increments it).
+ * forward: as hn_det_forward, but every BatchNorm normalises with the statistics of all n_images * height * width
+ *   pixels of the call (biased variance) and moves its running statistics in place:
+ *   running <- (1 - momentum) running + momentum batch, with the unbiased variance for running_var.
+ *   d_score [n,H,W], d_ori [n,H,W,2]; d_saved keeps the pre-norm activations, the statistics, and the soft NMS's
+ *   e, s and window arg-max (the first maximum in raster order, torch's max_pool2d rule) for the backward.
+ * backward: d_dscore [n,H,W], d_dori [n,H,W,2] (either may be NULL: zero) -> d_grads, a host array parallel to
+ *   d_tensors: every parameter slot needs a buffer (frozen parameters included; overwritten), the running
+ *   statistics' slots are ignored (may be NULL).  No image gradient.  The window maximum is not detached: its
+ *   gradient is routed to the arg-max, as autograd routes it through max_pool2d.
+ * Every sum over pixels (BatchNorm / InstanceNorm statistics, their backward sums, every weight and bias gradient)
+ * is a per-workgroup fp64 partial combined in a fixed order, no float atomics: outputs, running statistics and
+ * gradients are bit-identical call to call.
+ * Workspaces from hn_det_train_workspace_bytes; d_saved is written by the forward and read by its backward,
+ * d_scratch is transient; a short one is HN_ERR_WORKSPACE.  Caller's stream, no allocation or synchronisation
+ * inside; every argument check runs before the GPU is touched: n_images in 1 .. 2^24, height, width >= 1,
+ * height * width < 2^31, n_images * height * width >= 2 (the unbiased variance), bn_eps, in_eps > 0, momentum in
+ * 0 .. 1, no NULL pointer but d_dscore / d_dori, and d_images, d_score, d_ori, d_dscore, d_dori, d_saved and
+ * d_scratch 16-byte aligned. */
+#define HN_DET_TRAIN_TENSORS 40
+int hn_det_train_workspace_bytes(int64_t n_images, int32_t height, int32_t width, size_t* saved_bytes_out,
+                                 size_t* scratch_bytes_out);
+int hn_det_train_forward(const float* d_images, int64_t n_images, int32_t height, int32_t width,
+                         float* const* d_tensors, float bn_eps, float in_eps, float momentum, float* d_score,
+                         float* d_ori, void* d_saved, size_t saved_bytes, void* d_scratch, size_t scratch_bytes,
+                         void* hip_stream);
+int hn_det_train_backward(const float* d_dscore, const float* d_dori, const float* d_images, int64_t n_images,
+                          int32_t height, int32_t width, float* const* d_tensors, float* const* d_grads,
+                          void* d_saved, size_t saved_bytes, void* d_scratch, size_t scratch_bytes, void* hip_stream);
+
 /* Keypoint selection, the step between the detector's score map and hn_clip_patch: RFDet.process followed by
  * Network.inference's second topk_map, nonzero() and gathers (model/det.py:96-133, model/network.py:155-183,
  * utils/image_utils.py:197-274) for any score map d_score [n_images,height,width] fp32, K = topk:
