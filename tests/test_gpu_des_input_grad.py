@@ -20,6 +20,7 @@ from hardnetnas_amd import _native as N
 from hardnetnas_amd import network as NW
 from hardnetnas_amd import patches as PT
 from hardnetnas_amd import synth
+from nas_train_ref import raw_step
 
 pytestmark = pytest.mark.gpu
 FDL = ["fdl_NASNet", "fdl_NASNet_01"]
@@ -69,36 +70,6 @@ def test_parameter_gradients_and_statistics_do_not_change(name, cuda_device):
         assert torch.equal(g, res[1][1][k]), k
     for k, t in res[0][2].items():
         assert torch.equal(t, res[1][2][k]), k
-
-
-def raw_step(m, x, v, entry, din=None):
-    """One hn_nas_train_forward + backward through the C ABI on clones of the module's tensors: ``entry`` is
-    "hn_nas_train_backward" or "hn_nas_train_backward_dx" (with ``din``, a tensor or None).  Returns the
-    gradient buffers of every tensor slot."""
-    lib = N.load_library()
-    dev, b = x.device, x.shape[0]
-    desc = N.desc_for_module(m)
-    ts = [t.detach().clone() for t in N.train_tensors(m)[1]]
-    sv, sc = ctypes.c_size_t(), ctypes.c_size_t()
-    assert lib.hn_nas_train_workspace_bytes(ctypes.byref(desc), b, ctypes.byref(sv), ctypes.byref(sc)) == 0
-    saved = torch.empty(sv.value, device=dev, dtype=torch.uint8)
-    scratch = torch.empty(sc.value, device=dev, dtype=torch.uint8)
-    out = torch.empty((b, 128), device=dev)
-    ptrs = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-    rc = lib.hn_nas_train_forward(ctypes.byref(desc), x.data_ptr(), b, ptrs, 0.1, None, out.data_ptr(),
-                                  saved.data_ptr(), saved.numel(), scratch.data_ptr(), scratch.numel(), None)
-    assert rc == 0, lib.hn_last_error()
-    grads = [torch.zeros_like(t) for t in ts]
-    gp = (ctypes.c_void_p * len(ts))(*[g.data_ptr() for g in grads])
-    head = (ctypes.byref(desc), v.data_ptr(), x.data_ptr(), b, ptrs, None, gp, None)
-    tail = (saved.data_ptr(), saved.numel(), scratch.data_ptr(), scratch.numel(), None)
-    if entry == "hn_nas_train_backward":
-        rc = lib.hn_nas_train_backward(*head, *tail)
-    else:
-        rc = lib.hn_nas_train_backward_dx(*head, din.data_ptr() if din is not None else None, *tail)
-    assert rc == 0, lib.hn_last_error()
-    torch.cuda.synchronize()
-    return grads
 
 
 @pytest.mark.parametrize("name", FDL + ["wang2"])

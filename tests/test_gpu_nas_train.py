@@ -7,7 +7,10 @@ Bars: descriptors 1e-4 max abs (north_star), running statistics 1e-5 relative, t
 gradients of all parameters together L2-relative 5e-3 against the reference's fp64 step, and every
 single tensor's within 2e-2 (or 3x the reference's own fp32 error on it): a ReLU kink moves one
 small tensor (an SE / BN bias summing few entries) by percent in any fp32 implementation
-(tests/fixtures.py::nas_grad_check; wang2 measures 1.5e-5 on every tensor)."""
+(tests/fixtures.py::nas_grad_check; wang2 measures 1.5e-5 on every tensor).
+
+Every batch here is a multiple of 32; ragged batches (2, 3, 5, 6, 37), every op alone at every layer and the
+workspace guards of this path are in tests/test_gpu_nas_train_shapes.py."""
 import numpy as np
 import pytest
 import torch
