@@ -2,10 +2,14 @@
 //
 // Host-side responsibilities: validate the architecture and the flat parameter blob,
 // fold eval-mode BatchNorm into conv weight + bias (in double), pack weights into the
-// device layouts the kernels consume, and sequence the kernel launches of one forward
-// on the caller's stream over fixed-size patch chunks.
+// device layouts the kernels consume (hn_pack.h), and sequence the kernel launches of one
+// forward on the caller's stream over fixed-size patch chunks.  The model-less entry points
+// are in hn_api_det.hip (detector, keypoint selection, ground truth), hn_api_train.hip (train
+// steps and their losses) and hn_api_ops.hip (patch extraction, pair distance, matching, eval).
 #include "hardnet_mi355x.h"
+#include "hn_api_util.h"
 #include "hn_internal.h"
+#include "hn_pack.h"
 
 #include <algorithm>
 #include <atomic>
@@ -111,17 +115,10 @@ hipError_t hn_resident_blocks(const void* fn, int nthreads, int lds, int* reside
   return hipSuccess;
 }
 
-static int fail(int code, const std::string& msg) {
+int hn_fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
-
-#define HIPCHK(x)                                                                          \
-  do {                                                                                     \
-    hipError_t e_ = (x);                                                                   \
-    if (e_ != hipSuccess)                                                                  \
-      return fail(HN_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_));             \
-  } while (0)
 
 // candidate op table, restating hardnetNAS/fbnet_building_blocks/fbnet_builder.py:36-191
 // for CANDIDATE_BLOCKS (lookup_table_builder.py:18-20), in that index order.
@@ -168,38 +165,6 @@ struct Cursor {
     return r;
   }
 };
-
-uint16_t f2bf(float x) {  // round-to-nearest-even, as v_cvt_pk_bf16_f32
-  uint32_t u;
-  std::memcpy(&u, &x, 4);
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-float bf2f(uint16_t b) {
-  uint32_t u = (uint32_t)b << 16;
-  float f;
-  std::memcpy(&f, &u, 4);
-  return f;
-}
-
-// eval BatchNorm folded into the preceding bias-free conv:
-//   y = (conv(x) - mean) * gamma / sqrt(var + eps) + beta
-struct Folded {
-  std::vector<float> w, b;
-};
-Folded fold(const float* w, size_t per_out, int cout, const float* gamma, const float* beta,
-            const float* mean, const float* var, float eps) {
-  Folded f;
-  f.w.resize((size_t)cout * per_out);
-  f.b.resize(cout);
-  for (int n = 0; n < cout; ++n) {
-    const double sc = (gamma ? (double)gamma[n] : 1.0) / std::sqrt((double)var[n] + (double)eps);
-    for (size_t j = 0; j < per_out; ++j)
-      f.w[(size_t)n * per_out + j] = (float)((double)w[(size_t)n * per_out + j] * sc);
-    f.b[n] = (float)((beta ? (double)beta[n] : 0.0) - (double)mean[n] * sc);
-  }
-  return f;
-}
 
 struct Prof {
   bool on = false;
@@ -397,307 +362,8 @@ extern "C" int hn_param_count(const hn_arch_desc* desc, size_t* n_out) {
 }
 
 // ---------------------------------------------------------------------------------------
-// packing
+// model building: fold, pack (hn_pack.h) and upload
 // ---------------------------------------------------------------------------------------
-// conv1..5 of HardNet as bf16x3 MFMA fragments: [cc][tap][ks][nt][plane][lane][8]
-static std::vector<uint16_t> pack_conv3x3(const std::vector<float>& w, int cin, int cout) {
-  const int ncc = cin / 32, ntot = cout / 32;
-  std::vector<uint16_t> out((size_t)ncc * 9 * 2 * ntot * 2 * 64 * 8);
-  size_t o = 0;
-  for (int cc = 0; cc < ncc; ++cc)
-    for (int tap = 0; tap < 9; ++tap)
-      for (int ks = 0; ks < 2; ++ks)
-        for (int nt = 0; nt < ntot; ++nt) {
-          uint16_t* hi = &out[o];
-          uint16_t* lo = &out[o + 64 * 8];
-          for (int lane = 0; lane < 64; ++lane)
-            for (int j = 0; j < 8; ++j) {
-              const int n = nt * 32 + (lane & 31);
-              const int c = cc * 32 + ks * 16 + (lane >> 5) * 8 + j;
-              const float v = w[((size_t)n * cin + c) * 9 + tap];
-              const uint16_t h = f2bf(v);
-              hi[lane * 8 + j] = h;
-              lo[lane * 8 + j] = f2bf(v - bf2f(h));
-            }
-          o += 2 * 64 * 8;
-        }
-  return out;
-}
-
-// head conv (kernel kk x kk over an NHWC map): GEMM k = (y*kk + x)*cin + c,
-// fragments [ks][nt][plane][lane][8]
-// folded weights whose fp16 hi half is not finite (|w| >= 65520 or NaN): counted while a model is
-// packed (per calling thread), hn_create then fails instead of packing an infinite fragment
-static thread_local long tl_f16_out_of_range = 0;
-static void put_f16_split(float v, uint16_t* hi, uint16_t* lo) {  // hn_common.h split8_f16
-  const _Float16 hv = (_Float16)v;
-  if (!std::isfinite((float)hv)) ++tl_f16_out_of_range;
-  const _Float16 lv = (_Float16)(v - (float)hv);
-  std::memcpy(hi, &hv, 2);
-  std::memcpy(lo, &lv, 2);
-}
-
-static std::vector<uint16_t> pack_head(const std::vector<float>& w, int cin, int kk, bool f16 = false) {
-  const int K = cin * kk * kk;
-  std::vector<uint16_t> out((size_t)(K / 16) * 4 * 2 * 64 * 8);
-  size_t o = 0;
-  for (int ks = 0; ks < K / 16; ++ks)
-    for (int nt = 0; nt < 4; ++nt) {
-      uint16_t* hi = &out[o];
-      uint16_t* lo = &out[o + 64 * 8];
-      for (int lane = 0; lane < 64; ++lane)
-        for (int j = 0; j < 8; ++j) {
-          const int n = nt * 32 + (lane & 31);
-          const int k = ks * 16 + (lane >> 5) * 8 + j;
-          const int c = k % cin, yx = k / cin;
-          const float v = w[((size_t)n * cin + c) * kk * kk + yx];
-          if (f16) {
-            put_f16_split(v, &hi[lane * 8 + j], &lo[lane * 8 + j]);
-          } else {
-            const uint16_t h = f2bf(v);
-            hi[lane * 8 + j] = h;
-            lo[lane * 8 + j] = f2bf(v - bf2f(h));
-          }
-        }
-      o += 2 * 64 * 8;
-    }
-  return out;
-}
-
-// [cout][kg] -> [kg][cout]
-static std::vector<float> transpose_pw(const std::vector<float>& w, int cout, int kg) {
-  std::vector<float> t((size_t)kg * cout);
-  for (int n = 0; n < cout; ++n)
-    for (int k = 0; k < kg; ++k) t[(size_t)k * cout + n] = w[(size_t)n * kg + k];
-  return t;
-}
-
-
-// Fused-front stem weights as the MFMA A operand: [plane hi/lo][lane][8] fp16, lane
-// (r = l & 31 = output channel, h = l >> 5) holding taps 8h..8h+7 (taps >= 9 are zero).
-// The fused front's stem as 32x32x16 A operands [op][plane hi/lo][lane][8] fp16, lane (channel
-// r = l & 31, K slots 8 (l >> 5) ..): op 0 = the 9 taps in K slots 0..8 (one image row per MFMA);
-// op 1 = the same taps shifted to K slots 3..11, so that one B operand holding the 4 x 3 input
-// window of two adjacent rows (slot 3 dy + dx, dy = 0..3) feeds row y (op 0) and row y + 1 (op 1).
-static std::vector<uint16_t> pack_front_stem(const Folded& f) {
-  std::vector<uint16_t> a(2 * 2 * 64 * 8, 0);
-  for (int op = 0; op < 2; ++op)
-    for (int lane = 0; lane < 64; ++lane)
-      for (int j = 0; j < 8; ++j) {
-        const int r = lane & 31, tap = 8 * (lane >> 5) + j - 3 * op;
-        uint16_t* d = &a[(size_t)op * 2 * 64 * 8];
-        put_f16_split(tap >= 0 && tap < 9 ? f.w[(size_t)r * 9 + tap] : 0.f, &d[lane * 8 + j], &d[64 * 8 + lane * 8 + j]);
-      }
-  return a;
-}
-
-// Fused-front pw weights (fp16 hi/lo) as the MFMA A operand (rows = output channels in dw
-// order, i.e. after ChannelShuffle(g); grouped conv densified with zeros):
-// [MID/32][kstep][plane hi/lo][lane][8] fp16, lane (r = l & 31, h = l >> 5), element j
-// multiplying stem channel kappa(16*kstep + 8h + j) -- the order in which the stem MFMA
-// leaves its outputs in the lanes (C row (i & 3) + 8 (i >> 2) + 4h for i = 8*kstep + j).
-static void pack_front(const Folded& f, int mid, int g, std::vector<uint16_t>* a,
-                       std::vector<float>* bias) {
-  const int cin = 32, kg = cin / g, cg = mid / g;
-  auto src = [&](int d) { return g > 1 ? (d % g) * cg + d / g : d; };  // fbnet_builder.py:332-349
-  a->assign((size_t)mid / 32 * 2 * 2 * 64 * 8, 0);
-  bias->resize(mid);
-  for (int d = 0; d < mid; ++d) (*bias)[d] = f.b[src(d)];
-  for (int mc = 0; mc < mid / 32; ++mc)
-    for (int ks = 0; ks < 2; ++ks)
-      for (int lane = 0; lane < 64; ++lane)
-        for (int j = 0; j < 8; ++j) {
-          const int d = 32 * mc + (lane & 31), h = lane >> 5;
-          const int k = (j & 3) + 8 * (2 * ks + (j >> 2)) + 4 * h;  // stem channel
-          const int c = src(d), grp = c / (mid / g);
-          const float v = (k >= grp * kg && k < (grp + 1) * kg) ? f.w[(size_t)c * kg + (k - grp * kg)] : 0.f;
-          const size_t o = ((((size_t)mc * 2 + ks) * 2) * 64 + lane) * 8 + j;
-          put_f16_split(v, &(*a)[o], &(*a)[o + 64 * 8]);
-        }
-}
-
-// 1x1 conv [cout][cin/g] (groups densified with zeros, output rows permuted by row_src) as
-// the fp16x3 MFMA A operand: [cout/32][cin/16][plane][lane][8], lane (r = l & 31, h = l >> 5)
-// holding W[row_src(32t + r)][16s + 8h + j].
-template <class RowSrc>
-static std::vector<uint16_t> pack_1x1_a(const std::vector<float>& w, int cout, int cin, int g,
-                                        RowSrc row_src) {
-  const int kg = cin / g;
-  std::vector<uint16_t> a((size_t)cout / 32 * (cin / 16) * 2 * 64 * 8, 0);
-  for (int tt = 0; tt < cout / 32; ++tt)
-    for (int ks = 0; ks < cin / 16; ++ks)
-      for (int lane = 0; lane < 64; ++lane)
-        for (int j = 0; j < 8; ++j) {
-          const int c = row_src(32 * tt + (lane & 31)), k = 16 * ks + 8 * (lane >> 5) + j;
-          const int grp = c / (cout / g);
-          const float v = (k >= grp * kg && k < (grp + 1) * kg) ? w[(size_t)c * kg + (k - grp * kg)] : 0.f;
-          const size_t o = ((((size_t)tt * (cin / 16) + ks) * 2) * 64 + lane) * 8 + j;
-          put_f16_split(v, &a[o], &a[o + 64 * 8]);
-        }
-  return a;
-}
-
-// 1x1 conv (cout = 32, groups densified) as 16x16x32 fp16 hi/lo A operands: [cin/32][out tile 2][plane]
-// [lane 64][8], lane (row = l & 15 -> output channel 16 tile + row, k-group l >> 4 -> input
-// channels 32 chunk + 8 (l >> 4) + j) -- the NAS front's pwl (hn_front.hip, no-fold form)
-static std::vector<uint16_t> pack_1x1_a16(const std::vector<float>& w, int cout, int cin, int g) {
-  const int kg = cin / g;
-  std::vector<uint16_t> a((size_t)cin / 32 * (cout / 16) * 2 * 64 * 8, 0);
-  for (int ch = 0; ch < cin / 32; ++ch)
-    for (int tt = 0; tt < cout / 16; ++tt)
-      for (int lane = 0; lane < 64; ++lane)
-        for (int j = 0; j < 8; ++j) {
-          const int c = 16 * tt + (lane & 15), k = 32 * ch + 8 * (lane >> 4) + j;
-          const int grp = c / (cout / g);
-          const float v = (k >= grp * kg && k < (grp + 1) * kg) ? w[(size_t)c * kg + (k - grp * kg)] : 0.f;
-          const size_t o = ((((size_t)ch * (cout / 16) + tt) * 2) * 64 + lane) * 8 + j;
-          put_f16_split(v, &a[o], &a[o + 64 * 8]);
-        }
-  return a;
-}
-
-// 3x3 conv (cin = 32, BN folded) as 16x16x32 bf16 hi/lo A operands for k_c12:
-// [tap 9][group of 16 output channels][plane][lane 64][8], lane (row = l & 15 -> output
-// channel 16 g + row, k-group l >> 4 -> input channels 8 (l >> 4) + j).
-static std::vector<uint16_t> pack_c12(const std::vector<float>& w, int cout) {
-  const int cin = 32, ng = cout / 16;
-  std::vector<uint16_t> a((size_t)9 * ng * 2 * 64 * 8);
-  for (int tap = 0; tap < 9; ++tap)
-    for (int g = 0; g < ng; ++g)
-      for (int lane = 0; lane < 64; ++lane)
-        for (int j = 0; j < 8; ++j) {
-          const int oc = 16 * g + (lane & 15), ic = 8 * (lane >> 4) + j;
-          const float v = w[((size_t)oc * cin + ic) * 9 + tap];
-          const uint16_t hv = f2bf(v);
-          const size_t o = (((size_t)tap * ng + g) * 2 * 64 + lane) * 8 + j;
-          a[o] = hv;
-          a[o + 64 * 8] = f2bf(v - bf2f(hv));
-        }
-  return a;
-}
-
-// conv1 (cin = cout = 32, BN folded) as 1-D Winograd F(4,3) along x for k_c12w (hn_c12w.hip):
-// Toom-Cook points 0, 1, -1, 1/2, -1/2, inf; U_xi[ky] = sum_kx G[xi][kx] W[ky][kx] in fp64, bf16
-// hi / lo 16x16x32 A fragments [xi 6][ky 3][group 2][plane][lane 64][8], lane (row = l & 15 ->
-// output channel 16 g + row, k-group l >> 4 -> input channels 8 (l >> 4) + j)
-static std::vector<uint16_t> pack_c12w(const std::vector<float>& w) {
-  static const double G[6][3] = {{4, 0, 0},           {2.0 / 3, 2.0 / 3, 2.0 / 3},   {2.0 / 3, -2.0 / 3, 2.0 / 3},
-                                 {-8.0 / 3, -4.0 / 3, -2.0 / 3}, {-8.0 / 3, 4.0 / 3, -2.0 / 3}, {0, 0, 1}};
-  std::vector<uint16_t> a((size_t)6 * 3 * 2 * 2 * 64 * 8);
-  for (int xi = 0; xi < 6; ++xi)
-    for (int ky = 0; ky < 3; ++ky)
-      for (int g = 0; g < 2; ++g)
-        for (int lane = 0; lane < 64; ++lane)
-          for (int j = 0; j < 8; ++j) {
-            const int oc = 16 * g + (lane & 15), ic = 8 * (lane >> 4) + j;
-            double u = 0;
-            for (int kx = 0; kx < 3; ++kx) u += G[xi][kx] * (double)w[((size_t)oc * 32 + ic) * 9 + ky * 3 + kx];
-            const float v = (float)u;
-            const uint16_t hv = f2bf(v);
-            const size_t o = ((((size_t)(xi * 3 + ky) * 2 + g) * 2) * 64 + lane) * 8 + j;
-            a[o] = hv;
-            a[o + 64 * 8] = f2bf(v - bf2f(hv));
-          }
-  return a;
-}
-
-// stride-1 3x3 conv (BN folded) as 1-D Winograd F(2,3) along x (hn_wino1.hip): U_xi[ky] =
-// sum_kx G[xi][kx] W[ky][kx] in fp64 (U3 negated: it accumulates into the odd output column with a
-// minus sign), bf16 hi / lo A fragments [cin/32][xi][ky][ks][cout/32][plane][lane][8] in the
-// kernel's K-step order kx = 6 xi + 2 ky + ks
-static std::vector<uint16_t> pack_wino1(const std::vector<float>& w, int cin, int cout) {
-  static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-  const int ncc = cin / 32, ntot = cout / 32;
-  std::vector<uint16_t> out((size_t)ncc * 24 * ntot * 2 * 64 * 8);
-  size_t o = 0;
-  for (int cc = 0; cc < ncc; ++cc)
-    for (int kx = 0; kx < 24; ++kx)
-      for (int nt = 0; nt < ntot; ++nt) {
-        const int xi = kx / 6, ky = (kx % 6) / 2, ks = kx % 2;
-        uint16_t* hi = &out[o];
-        uint16_t* lo = &out[o + 64 * 8];
-        for (int lane = 0; lane < 64; ++lane)
-          for (int j = 0; j < 8; ++j) {
-            const int n = nt * 32 + (lane & 31);
-            const int c = cc * 32 + ks * 16 + (lane >> 5) * 8 + j;
-            double u = 0;
-            for (int t = 0; t < 3; ++t) u += G[xi][t] * (double)w[((size_t)n * cin + c) * 9 + ky * 3 + t];
-            const float v = (float)(xi == 3 ? -u : u);
-            const uint16_t hv = f2bf(v);
-            hi[lane * 8 + j] = hv;
-            lo[lane * 8 + j] = f2bf(v - bf2f(hv));
-          }
-        o += 2 * 64 * 8;
-      }
-  return out;
-}
-
-// stride-1 3x3 conv (BN folded) as 1-D Winograd F(4,3) along x (hn_wino1.hip k_conv_w4): U_xi[ky] =
-// sum_kx G[xi][kx] W[ky][kx] in fp64, bf16 hi / lo A fragments of the 16x16x32 MFMA
-// [cin/32][kx 18][cout/16][plane][lane][8] in the kernel's K-step order kx = 3 xo + ky, xi = w4_xi(xo)
-// (lane: output channel 16 nt + (lane & 15), input channels 32 cc + 8 (lane >> 4) + j)
-static std::vector<uint16_t> pack_wino4(const std::vector<float>& w, int cin, int cout) {
-  static const double G[6][3] = {{4, 0, 0},
-                                 {2.0 / 3, 2.0 / 3, 2.0 / 3},
-                                 {2.0 / 3, -2.0 / 3, 2.0 / 3},
-                                 {-8.0 / 3, -4.0 / 3, -2.0 / 3},
-                                 {-8.0 / 3, 4.0 / 3, -2.0 / 3},
-                                 {0, 0, 1}};
-  static const int XO[6] = {0, 5, 1, 2, 3, 4};
-  const int ncc = cin / 32, ntot = cout / 16;
-  std::vector<uint16_t> out((size_t)ncc * 18 * ntot * 2 * 64 * 8);
-  size_t o = 0;
-  for (int cc = 0; cc < ncc; ++cc)
-    for (int kx = 0; kx < 18; ++kx)
-      for (int nt = 0; nt < ntot; ++nt) {
-        const int xi = XO[kx / 3], ky = kx % 3;
-        uint16_t* hi = &out[o];
-        uint16_t* lo = &out[o + 64 * 8];
-        for (int lane = 0; lane < 64; ++lane)
-          for (int j = 0; j < 8; ++j) {
-            const int n = nt * 16 + (lane & 15);
-            const int c = cc * 32 + (lane >> 4) * 8 + j;
-            double u = 0;
-            for (int t = 0; t < 3; ++t) u += G[xi][t] * (double)w[((size_t)n * cin + c) * 9 + ky * 3 + t];
-            const float v = (float)u;
-            const uint16_t hv = f2bf(v);
-            hi[lane * 8 + j] = hv;
-            lo[lane * 8 + j] = f2bf(v - bf2f(hv));
-          }
-        o += 2 * 64 * 8;
-      }
-  return out;
-}
-
-#ifdef HN_EXPERIMENTS
-// stride-1 3x3 conv (BN folded) as Winograd F(2x2,3x3) U = G g G^T (fp64, then bf16 hi/lo),
-// packed as the B operand of hn_wino.hip's 32x32x16 MFMAs: [cout/32][cin/16][xi 16][plane][lane
-// 64][8], lane (column l & 31 -> output channel, k-group l >> 5 -> input channels 8 (l >> 5) + j)
-static std::vector<uint16_t> pack_wino(const std::vector<float>& w, int cin, int cout) {
-  static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-  const int ncb = cout / 32, nks = cin / 16;
-  std::vector<uint16_t> a((size_t)ncb * nks * 16 * 2 * 64 * 8);
-  for (int cb = 0; cb < ncb; ++cb)
-    for (int ks = 0; ks < nks; ++ks)
-      for (int xi = 0; xi < 16; ++xi)
-        for (int lane = 0; lane < 64; ++lane)
-          for (int j = 0; j < 8; ++j) {
-            const int co = 32 * cb + (lane & 31), ci = 16 * ks + 8 * (lane >> 5) + j;
-            const float* g = &w[((size_t)co * cin + ci) * 9];
-            const int i0 = xi >> 2, j0 = xi & 3;
-            double u = 0;
-            for (int r = 0; r < 3; ++r)
-              for (int c = 0; c < 3; ++c) u += G[i0][r] * (double)g[r * 3 + c] * G[j0][c];
-            const float v = (float)u;
-            const uint16_t hv = f2bf(v);
-            const size_t o = ((((size_t)(cb * nks + ks) * 16 + xi) * 2) * 64 + lane) * 8 + j;
-            a[o] = hv;
-            a[o + 64 * 8] = f2bf(v - bf2f(hv));
-          }
-  return a;
-}
-#endif
-
 static int build_hardnet(hn_model* m, Cursor& cur) {
   static const int cin[7] = {1, 32, 32, 64, 64, 128, 128};
   static const int cout[7] = {32, 32, 64, 64, 128, 128, 128};
@@ -769,14 +435,6 @@ static int take_cbr(hn_model* m, Cursor& cur, int cout, size_t per_out, Folded* 
 }
 
 static int build_nas_layers(hn_model* m, Cursor& cur, int hw, size_t maxf);
-
-// stem [32][9] -> [tap][32] for the VALU stem / front kernels
-static std::vector<float> stem_taps(const std::vector<float>& w) {
-  std::vector<float> sw(9 * 32);
-  for (int n = 0; n < 32; ++n)
-    for (int t = 0; t < 9; ++t) sw[t * 32 + n] = w[n * 9 + t];
-  return sw;
-}
 
 static int build_nas(hn_model* m, Cursor& cur) {
   int rc;
@@ -1344,13 +1002,10 @@ extern "C" int hn_forward(hn_model* m, const float* d_in, int64_t batch, float* 
   if (batch < 0) return fail(HN_ERR_ARG, "negative batch");
   if (batch == 0) return HN_OK;
   if (!d_in || !d_out || !d_workspace) return fail(HN_ERR_ARG, "NULL device pointer");
-  if ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out) |
-       reinterpret_cast<uintptr_t>(d_workspace)) & 15)
-    return fail(HN_ERR_ARG, "device pointers must be 16-byte aligned");
+  if (hn_misaligned(16, d_in, d_out, d_workspace)) return fail(HN_ERR_ARG, "device pointers must be 16-byte aligned");
   size_t need = 0;
   hn_workspace_bytes(m, batch, &need);
-  if (workspace_bytes < need)
-    return fail(HN_ERR_WORKSPACE, "workspace too small: need " + std::to_string(need) + " bytes");
+  if (int rc = hn_need_ws(workspace_bytes, need)) return rc;
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
   KnobScope knobs(&m->knobs);
   TileScope tiles(m, st);
@@ -1398,22 +1053,14 @@ extern "C" int hn_forward_u8(hn_model* m, const uint8_t* d_in, int64_t batch, in
                              size_t workspace_bytes, void* hip_stream) {
   if (!m) return fail(HN_ERR_ARG, "model is NULL");
   if (batch < 0) return fail(HN_ERR_ARG, "negative batch");
-  if (resize != HN_RESIZE_NONE && resize != HN_RESIZE_CV2_LINEAR && resize != HN_RESIZE_PIL_BILINEAR)
-    return fail(HN_ERR_ARG, "unknown resize mode " + std::to_string(resize));
-  const int want = resize == HN_RESIZE_NONE ? 32 : 64;
-  if (in_hw != want)
-    return fail(HN_ERR_ARG, "in_hw must be " + std::to_string(want) + " for this resize mode, got " +
-                                std::to_string(in_hw));
+  if (int rc = hn_resize_args(resize, in_hw)) return rc;
   if (normalize && !(stdv != 0.0f)) return fail(HN_ERR_ARG, "std must be nonzero");
   if (batch == 0) return HN_OK;
   if (!d_in || !d_out || !d_workspace) return fail(HN_ERR_ARG, "NULL device pointer");
-  if ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out) |
-       reinterpret_cast<uintptr_t>(d_workspace)) & 15)
-    return fail(HN_ERR_ARG, "device pointers must be 16-byte aligned");
+  if (hn_misaligned(16, d_in, d_out, d_workspace)) return fail(HN_ERR_ARG, "device pointers must be 16-byte aligned");
   size_t need = 0;
   hn_workspace_bytes_u8(m, batch, &need);
-  if (workspace_bytes < need)
-    return fail(HN_ERR_WORKSPACE, "workspace too small: need " + std::to_string(need) + " bytes");
+  if (int rc = hn_need_ws(workspace_bytes, need)) return rc;
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
   KnobScope knobs(&m->knobs);
   TileScope tiles(m, st);
@@ -1443,46 +1090,6 @@ extern "C" int hn_forward_u8(hn_model* m, const uint8_t* d_in, int64_t batch, in
   return HN_OK;
 }
 
-// keypoint patch extraction (hn_clip.hip): what hn_clip_patch and hn_forward_kp check about the images and
-// the keypoint list before the GPU is touched; null = fine
-static const char* clip_arg_error(int64_t n_images, int32_t height, int32_t width, int64_t n) {
-  if (n < 0) return "n must be >= 0";
-  if (n_images < 0) return "n_images must be >= 0";
-  if (height < 2 || width < 2) return "height and width must be >= 2";
-  // n_images * height * width < 2^63: the flat index of every pixel fits an int64
-  if (n_images > INT64_MAX / ((int64_t)height * (int64_t)width)) return "n_images * height * width must be below 2^63";
-  if (n > 0 && n_images == 0) return "n_images must be >= 1 for n > 0 keypoints";
-  return nullptr;
-}
-
-extern "C" int hn_clip_patch(const float* d_images, int64_t n_images, int32_t height, int32_t width,
-                             const int64_t* d_kpts, const float* d_scale, const float* d_ori, const float* d_ratio,
-                             int64_t n, float* d_patches, void* hip_stream) {
-  if (const char* e = clip_arg_error(n_images, height, width, n)) return fail(HN_ERR_ARG, e);
-  if (n == 0) return HN_OK;
-  if (!d_images || !d_kpts || !d_scale || !d_ratio || !d_patches)
-    return fail(HN_ERR_ARG, "NULL device pointer (only d_ori may be NULL)");
-  if (reinterpret_cast<uintptr_t>(d_patches) & 15) return fail(HN_ERR_ARG, "d_patches must be 16-byte aligned");
-  HIPCHK(hn_launch_clip(d_images, n_images, height, width, d_kpts, d_scale, d_ori, d_ratio, n, d_patches,
-                        static_cast<hipStream_t>(hip_stream)));
-  return HN_OK;
-}
-
-extern "C" int hn_clip_patch_backward(const float* d_dpatches, const float* d_images, int64_t n_images, int32_t height,
-                                      int32_t width, const int64_t* d_kpts, const float* d_scale, const float* d_ori,
-                                      const float* d_ratio, int64_t n, float* d_dscale, float* d_dori,
-                                      void* hip_stream) {
-  if (const char* e = clip_arg_error(n_images, height, width, n)) return fail(HN_ERR_ARG, e);
-  if (d_dori && !d_ori) return fail(HN_ERR_ARG, "d_dori needs d_ori (no rotation has no orientation gradient)");
-  if (n == 0) return HN_OK;
-  if (!d_dpatches || !d_images || !d_kpts || !d_scale || !d_ratio)
-    return fail(HN_ERR_ARG, "NULL device pointer (only d_ori, d_dscale and d_dori may be NULL)");
-  if (reinterpret_cast<uintptr_t>(d_dpatches) & 15) return fail(HN_ERR_ARG, "d_dpatches must be 16-byte aligned");
-  HIPCHK(hn_launch_clip_backward(d_dpatches, d_images, n_images, height, width, d_kpts, d_scale, d_ori, d_ratio, n,
-                                 d_dscale, d_dori, static_cast<hipStream_t>(hip_stream)));
-  return HN_OK;
-}
-
 extern "C" int hn_workspace_bytes_kp(const hn_model* m, int64_t n, size_t* bytes_out) {
   int rc = hn_workspace_bytes(m, n, bytes_out);
   if (rc) return rc;
@@ -1500,12 +1107,11 @@ extern "C" int hn_forward_kp(hn_model* m, const float* d_images, int64_t n_image
   if (n == 0) return HN_OK;
   if (!d_images || !d_kpts || !d_scale || !d_ratio || !d_out || !d_workspace)
     return fail(HN_ERR_ARG, "NULL device pointer (only d_ori may be NULL)");
-  if ((reinterpret_cast<uintptr_t>(d_out) | reinterpret_cast<uintptr_t>(d_workspace)) & 15)
+  if (hn_misaligned(16, d_out, d_workspace))
     return fail(HN_ERR_ARG, "d_out / d_workspace must be 16-byte aligned");
   size_t need = 0, base = 0;
   hn_workspace_bytes_kp(m, n, &need);
-  if (workspace_bytes < need)
-    return fail(HN_ERR_WORKSPACE, "workspace too small: need " + std::to_string(need) + " bytes");
+  if (int rc = hn_need_ws(workspace_bytes, need)) return rc;
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
   KnobScope knobs(&m->knobs);
   TileScope tiles(m, st);
@@ -1521,734 +1127,6 @@ extern "C" int hn_forward_kp(hn_model* m, const float* d_images, int64_t n_image
                                                    : forward_nas(m, patches, P, pmax, d_out + off * 128, ws, st);
     if (rc) return rc;
   }
-  return HN_OK;
-}
-
-// ---------------------------------------------------------------------------------------
-// FDLNet's NASNet keypoint detector (hn_det.hip) and keypoint selection (hn_select.hip)
-// ---------------------------------------------------------------------------------------
-struct hn_detector {
-  float* params = nullptr;  // hndet layout, BN folded
-  float in_eps = 1e-5f;
-};
-
-extern "C" int hn_det_param_count(size_t* n_out) {
-  if (!n_out) return fail(HN_ERR_ARG, "n_out is NULL");
-  *n_out = hndet::kStateFloats;
-  return HN_OK;
-}
-
-extern "C" int hn_det_create(const float* host_params, size_t n_params, float bn_eps, float in_eps,
-                             hn_detector** out) {
-  using namespace hndet;
-  if (!out || !host_params) return fail(HN_ERR_ARG, "NULL argument");
-  *out = nullptr;
-  if (n_params != (size_t)kStateFloats)
-    return fail(HN_ERR_ARG, "host_params has " + std::to_string(n_params) + " floats, expected " +
-                                std::to_string(kStateFloats));
-  if (!(bn_eps > 0.f) || !(in_eps > 0.f)) return fail(HN_ERR_ARG, "bn_eps and in_eps must be > 0");
-  for (size_t i = 0; i < n_params; ++i)
-    if (!std::isfinite(host_params[i])) return fail(HN_ERR_ARG, "host_params holds a non-finite value");
-  std::vector<float> f(kFolded);
-  const float* p = host_params;
-  std::memcpy(&f[kC0W], p, 160 * sizeof(float));  // features.0.weight, .bias
-  p += 160;
-  // conv weight [cout][per] without bias, then BatchNorm weight, bias, running_mean, running_var [cout]
-  auto conv_bn = [&](int cout, int per, float* w, float* b) -> bool {
-    const float *cw = p, *g = p + cout * per, *be = g + cout, *rm = be + cout, *rv = rm + cout;
-    p = rv + cout;
-    for (int o = 0; o < cout; ++o) {
-      if (!((double)rv[o] + bn_eps > 0)) return false;
-      const double s = (double)g[o] / std::sqrt((double)rv[o] + (double)bn_eps);
-      for (int k = 0; k < per; ++k) w[o * per + k] = (float)((double)cw[o * per + k] * s);
-      b[o] = (float)((double)be[o] - (double)rm[o] * s);
-    }
-    return true;
-  };
-  for (int k = 0; k < 2; ++k) {
-    float* blk = &f[kBlk + k * kBlkSize];
-    if (!conv_bn(8, 8, blk + kBlkPw1W, blk + kBlkPw1B) || !conv_bn(8, 9, blk + kBlkDwW, blk + kBlkDwB) ||
-        !conv_bn(8, 8, blk + kBlkPw2W, blk + kBlkPw2B))
-      return fail(HN_ERR_ARG, "a BatchNorm running_var + bn_eps is not positive");
-  }
-  std::memcpy(&f[kHeadW], p, 144 * sizeof(float));  // conv.weight
-  f[kHeadB] = p[144];                               // conv.bias
-  f[kInG] = p[145];                                 // insnorm.weight, .bias
-  f[kInB] = p[146];
-  p += 147;
-  std::memcpy(&f[kHeadW + 144], p, 288 * sizeof(float));  // conv_ori.weight
-  f[kHeadB + 1] = p[288];                                 // conv_ori.bias
-  f[kHeadB + 2] = p[289];
-  f[kInG + 1] = p[290];                                   // insnorm_ori.weight, .bias
-  f[kInG + 2] = p[291];
-  f[kInB + 1] = p[292];
-  f[kInB + 2] = p[293];
-  p += 294;
-  if ((size_t)(p - host_params) != n_params) return fail(HN_ERR_ARG, "host_params not fully consumed");
-  hn_detector* d = new hn_detector;
-  d->in_eps = in_eps;
-  if (hipMalloc(&d->params, kFolded * sizeof(float)) != hipSuccess) {
-    delete d;
-    return fail(HN_ERR_NOMEM, "hipMalloc of parameters failed");
-  }
-  const hipError_t e = hipMemcpy(d->params, f.data(), kFolded * sizeof(float), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    (void)hipFree(d->params);
-    delete d;
-    return fail(HN_ERR_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
-  }
-  *out = d;
-  return HN_OK;
-}
-
-extern "C" void hn_det_destroy(hn_detector* d) {
-  if (!d) return;
-  (void)hipFree(d->params);
-  delete d;
-}
-
-// what hn_det_workspace_bytes and hn_det_forward check about the images; null = fine
-static const char* det_arg_error(int64_t n_images, int32_t height, int32_t width) {
-  if (n_images < 0) return "n_images must be >= 0";
-  if (height < 1 || width < 1 || (int64_t)height * width < 2)
-    return "height and width must be >= 1 with at least 2 pixels (InstanceNorm)";
-  if ((int64_t)height * width > INT32_MAX) return "height * width must be below 2^31";
-  if (n_images > INT32_MAX || n_images * hn_det_parts(height, width) > INT32_MAX)
-    return "n_images * tiles must be below 2^31";
-  return nullptr;
-}
-
-extern "C" int hn_det_workspace_bytes(int64_t n_images, int32_t height, int32_t width, size_t* bytes_out) {
-  if (!bytes_out) return fail(HN_ERR_ARG, "bytes_out is NULL");
-  if (const char* e = det_arg_error(n_images, height, width)) return fail(HN_ERR_ARG, e);
-  *bytes_out = hn_det_ws_bytes(n_images, height, width);
-  return HN_OK;
-}
-
-extern "C" int hn_det_forward(hn_detector* d, const float* d_images, int64_t n_images, int32_t height, int32_t width,
-                              float* d_score, float* d_ori, void* d_workspace, size_t workspace_bytes,
-                              void* hip_stream) {
-  if (const char* e = det_arg_error(n_images, height, width)) return fail(HN_ERR_ARG, e);
-  if (!d) return fail(HN_ERR_ARG, "detector is NULL");
-  if (n_images == 0) return HN_OK;
-  if (!d_images || !d_score || !d_ori || !d_workspace) return fail(HN_ERR_ARG, "NULL device pointer");
-  if ((reinterpret_cast<uintptr_t>(d_ori) & 7) || (reinterpret_cast<uintptr_t>(d_workspace) & 15))
-    return fail(HN_ERR_ARG, "d_ori must be 8-byte and d_workspace 16-byte aligned");
-  const size_t need = hn_det_ws_bytes(n_images, height, width);
-  if (workspace_bytes < need)
-    return fail(HN_ERR_WORKSPACE, "workspace too small: need " + std::to_string(need) + " bytes");
-  HIPCHK(hn_launch_det(d->params, d->in_eps, d_images, n_images, height, width, d_score, d_ori, d_workspace,
-                       static_cast<hipStream_t>(hip_stream)));
-  return HN_OK;
-}
-
-// the detector in train() (hn_det_train.hip): what the three entry points check about the images; null = fine
-static const char* det_train_arg_error(int64_t n_images, int32_t height, int32_t width) {
-  if (n_images < 1) return "n_images must be >= 1";
-  if (height < 1 || width < 1) return "height and width must be >= 1";
-  if ((int64_t)height * width > INT32_MAX) return "height * width must be below 2^31";
-  if (n_images > (1 << 24)) return "n_images must be at most 2^24";
-  if (n_images * height * width < 2) return "n_images * height * width must be >= 2 (the unbiased batch variance)";
-  return nullptr;
-}
-
-extern "C" int hn_det_train_workspace_bytes(int64_t n_images, int32_t height, int32_t width, size_t* saved_bytes_out,
-                                            size_t* scratch_bytes_out) {
-  if (!saved_bytes_out || !scratch_bytes_out) return fail(HN_ERR_ARG, "NULL size pointer");
-  if (const char* e = det_train_arg_error(n_images, height, width)) return fail(HN_ERR_ARG, e);
-  hn_det_train_plan(n_images, height, width, saved_bytes_out, scratch_bytes_out);
-  return HN_OK;
-}
-
-static int det_train_args(int64_t n_images, int32_t height, int32_t width, const float* images,
-                          float* const* tensors, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes) {
-  if (const char* e = det_train_arg_error(n_images, height, width)) return fail(HN_ERR_ARG, e);
-  if (!images || !saved || !scratch) return fail(HN_ERR_ARG, "NULL device pointer");
-  if ((reinterpret_cast<uintptr_t>(images) | reinterpret_cast<uintptr_t>(saved) |
-       reinterpret_cast<uintptr_t>(scratch)) & 15)
-    return fail(HN_ERR_ARG, "d_images, d_saved and d_scratch must be 16-byte aligned");
-  size_t need_sv = 0, need_sc = 0;
-  hn_det_train_plan(n_images, height, width, &need_sv, &need_sc);
-  if (saved_bytes < need_sv)
-    return fail(HN_ERR_WORKSPACE, "saved workspace too small: need " + std::to_string(need_sv) + " bytes");
-  if (scratch_bytes < need_sc)
-    return fail(HN_ERR_WORKSPACE, "scratch workspace too small: need " + std::to_string(need_sc) + " bytes");
-  if (!tensors) return fail(HN_ERR_ARG, "NULL tensor pointer array");
-  for (int i = 0; i < HN_DET_TRAIN_TENSORS; ++i)
-    if (!tensors[i]) return fail(HN_ERR_ARG, "NULL tensor pointer " + std::to_string(i));
-  return HN_OK;
-}
-
-extern "C" int hn_det_train_forward(const float* d_images, int64_t n_images, int32_t height, int32_t width,
-                                    float* const* d_tensors, float bn_eps, float in_eps, float momentum,
-                                    float* d_score, float* d_ori, void* d_saved, size_t saved_bytes, void* d_scratch,
-                                    size_t scratch_bytes, void* hip_stream) {
-  int rc = det_train_args(n_images, height, width, d_images, d_tensors, d_saved, saved_bytes, d_scratch,
-                          scratch_bytes);
-  if (rc) return rc;
-  if (!(bn_eps > 0.f) || !(in_eps > 0.f)) return fail(HN_ERR_ARG, "bn_eps and in_eps must be > 0");
-  if (!(momentum >= 0.f && momentum <= 1.f)) return fail(HN_ERR_ARG, "momentum must be in 0 .. 1");
-  if (!d_score || !d_ori) return fail(HN_ERR_ARG, "NULL device pointer");
-  if ((reinterpret_cast<uintptr_t>(d_score) | reinterpret_cast<uintptr_t>(d_ori)) & 15)
-    return fail(HN_ERR_ARG, "d_score and d_ori must be 16-byte aligned");
-  HIPCHK(hn_det_train_forward_impl(d_images, n_images, height, width, d_tensors, bn_eps, in_eps, momentum, d_score,
-                                   d_ori, static_cast<char*>(d_saved), static_cast<char*>(d_scratch),
-                                   static_cast<hipStream_t>(hip_stream)));
-  return HN_OK;
-}
-
-extern "C" int hn_det_train_backward(const float* d_dscore, const float* d_dori, const float* d_images,
-                                     int64_t n_images, int32_t height, int32_t width, float* const* d_tensors,
-                                     float* const* d_grads, void* d_saved, size_t saved_bytes, void* d_scratch,
-                                     size_t scratch_bytes, void* hip_stream) {
-  int rc = det_train_args(n_images, height, width, d_images, d_tensors, d_saved, saved_bytes, d_scratch,
-                          scratch_bytes);
-  if (rc) return rc;
-  if ((reinterpret_cast<uintptr_t>(d_dscore) | reinterpret_cast<uintptr_t>(d_dori)) & 15)
-    return fail(HN_ERR_ARG, "d_dscore and d_dori must be 16-byte aligned");
-  if (!d_grads) return fail(HN_ERR_ARG, "NULL gradient pointer array");
-  for (int i = 0; i < HN_DET_TRAIN_TENSORS; ++i)
-    if (hn_det_train_is_param(i) && !d_grads[i])
-      return fail(HN_ERR_ARG, "d_grads[" + std::to_string(i) + "] is NULL: every parameter slot needs a gradient buffer");
-  HIPCHK(hn_det_train_backward_impl(d_dscore, d_dori, d_images, n_images, height, width, d_tensors, d_grads,
-                                    static_cast<char*>(d_saved), static_cast<char*>(d_scratch),
-                                    static_cast<hipStream_t>(hip_stream)));
-  return HN_OK;
-}
-
-// what hn_select_workspace_bytes and hn_select_keypoints check about the map and K; null = fine
-static const char* select_arg_error(int64_t n_images, int32_t height, int32_t width, int32_t topk) {
-  if (n_images < 0) return "n_images must be >= 0";
-  if (height < 1 || width < 1) return "height and width must be >= 1";
-  if ((int64_t)height * width > INT32_MAX) return "height * width must be below 2^31";
-  if (n_images > INT32_MAX) return "n_images must be below 2^31";
-  if (topk < 1 || topk > (int64_t)height * width) return "topk must be in 1 .. height * width";
-  return nullptr;
-}
-
-extern "C" int hn_select_workspace_bytes(int64_t n_images, int32_t height, int32_t width, int32_t topk,
-                                         size_t* bytes_out) {
-  if (!bytes_out) return fail(HN_ERR_ARG, "bytes_out is NULL");
-  if (const char* e = select_arg_error(n_images, height, width, topk)) return fail(HN_ERR_ARG, e);
-  *bytes_out = hn_select_ws_bytes(n_images, height, width);
-  return HN_OK;
-}
-
-extern "C" int hn_select_keypoints(const float* d_score, int64_t n_images, int32_t height, int32_t width,
-                                   int32_t border, float nms_thresh, int32_t nms_ksize, int32_t topk,
-                                   int32_t gauss_ksize, float gauss_sigma, const float* d_scale_map,
-                                   float scale_value, const float* d_ori_map, int64_t* d_kpts, float* d_kscore,
-                                   float* d_kscale, float* d_kori, float* d_score_proc, uint8_t* d_topk_mask,
-                                   void* d_workspace, size_t workspace_bytes, void* hip_stream) {
-  if (const char* e = select_arg_error(n_images, height, width, topk)) return fail(HN_ERR_ARG, e);
-  if (border < 0 || height <= 2 * (int64_t)border || width <= 2 * (int64_t)border)
-    return fail(HN_ERR_ARG, "border must be >= 0 with height, width > 2 * border");
-  if (nms_ksize < 1 || nms_ksize > 15 || !(nms_ksize & 1)) return fail(HN_ERR_ARG, "nms_ksize must be odd, 1 .. 15");
-  if (gauss_ksize < 1 || gauss_ksize > 15 || !(gauss_ksize & 1))
-    return fail(HN_ERR_ARG, "gauss_ksize must be odd, 1 .. 15");
-  if (!(gauss_sigma >= 0.f) || !std::isfinite(gauss_sigma))
-    return fail(HN_ERR_ARG, "gauss_sigma must be finite and >= 0");
-  if (nms_thresh != nms_thresh) return fail(HN_ERR_ARG, "nms_thresh is NaN");
-  if ((d_kori == nullptr) != (d_ori_map == nullptr))
-    return fail(HN_ERR_ARG, "d_kori and d_ori_map must both be given or both NULL");
-  if (n_images == 0) return HN_OK;
-  if (!d_score || !d_kpts || !d_kscore || !d_kscale || !d_workspace)
-    return fail(HN_ERR_ARG, "NULL device pointer (d_scale_map, d_ori_map / d_kori, d_score_proc, d_topk_mask may be)");
-  if (reinterpret_cast<uintptr_t>(d_workspace) & 15) return fail(HN_ERR_ARG, "d_workspace must be 16-byte aligned");
-  const size_t need = hn_select_ws_bytes(n_images, height, width);
-  if (workspace_bytes < need)
-    return fail(HN_ERR_WORKSPACE, "workspace too small: need " + std::to_string(need) + " bytes");
-  // get_gauss_filter_weight (image_utils.py:277-295): the exponent in its fp32 operation order, the exponential as
-  // the fp64 one rounded to fp32 (what any libm reproduces); not normalised; sigma 0: a delta
-  float taps[225];
-  const int c = gauss_ksize / 2;
-  const float two_s2 = 2.0f * (gauss_sigma * gauss_sigma);
-  for (int y = 0; y < gauss_ksize; ++y)
-    for (int x = 0; x < gauss_ksize; ++x) {
-      const float fx = (float)(x - c), fy = (float)(y - c);
-      taps[y * gauss_ksize + x] = gauss_sigma == 0.f ? (x == c && y == c ? 1.f : 0.f)
-                                                     : (float)std::exp((double)-((fx * fx) / two_s2 + (fy * fy) / two_s2));
-    }
-  HnSelectArgs a{};
-  a.score = d_score;
-  a.B = n_images;
-  a.H = height;
-  a.W = width;
-  a.border = border;
-  a.nms_thresh = nms_thresh;
-  a.nms_ksize = nms_ksize;
-  a.topk = topk;
-  a.gauss_ksize = gauss_ksize;
-  a.taps = taps;
-  a.scale_map = d_scale_map;
-  a.scale_value = scale_value;
-  a.ori_map = d_ori_map;
-  a.kpts = d_kpts;
-  a.kscore = d_kscore;
-  a.kscale = d_kscale;
-  a.kori = d_kori;
-  a.score_proc = d_score_proc;
-  a.topk_mask = d_topk_mask;
-  a.ws = d_workspace;
-  HIPCHK(hn_launch_select(a, static_cast<hipStream_t>(hip_stream)));
-  return HN_OK;
-}
-
-// homography ground-truth stage (hn_gt.hip): what the four calls check about the maps before the GPU is touched;
-// null = fine.  height * width < 2^31 and n_images * height * width < 2^62 are hn_homo.h's conditions.
-static const char* gt_arg_error(int64_t n_images, int32_t height, int32_t width) {
-  if (n_images < 0) return "n_images must be >= 0";
-  if (height < 2 || width < 2) return "height and width must be >= 2";
-  if ((int64_t)height * width > INT32_MAX) return "height * width must be below 2^31";
-  if (n_images > ((int64_t)1 << 62) / ((int64_t)height * width)) return "n_images * height * width must be below 2^62";
-  return nullptr;
-}
-
-extern "C" int hn_warp_score(const float* d_score, const float* d_homo, int64_t n_images, int32_t height,
-                             int32_t width, int32_t border, int32_t align_corners, float* d_warped, float* d_visible,
-                             void* hip_stream) {
-  if (const char* e = gt_arg_error(n_images, height, width)) return fail(HN_ERR_ARG, e);
-  if (border < 0 || height <= 2 * (int64_t)border || width <= 2 * (int64_t)border)
-    return fail(HN_ERR_ARG, "border must be >= 0 with height, width > 2 * border");
-  if (align_corners != 0 && align_corners != 1) return fail(HN_ERR_ARG, "align_corners must be 0 or 1");
-  if (n_images == 0 || (!d_warped && !d_visible)) return HN_OK;
-  if (!d_homo || (d_warped && !d_score))
-    return fail(HN_ERR_ARG, "NULL device pointer (d_warped or d_visible may be; d_score only without d_warped)");
-  HIPCHK(hn_launch_warp_score(d_score, d_homo, n_images, height, width, border, align_corners, d_warped, d_visible,
-                              static_cast<hipStream_t>(hip_stream)));
-  return HN_OK;
-}
-
-extern "C" int hn_gt_scale_orin(const float* d_scale, float scale_value, const float* d_ori, const float* d_homo12,
-                                const float* d_homo21, int64_t n_images, int32_t height, int32_t width,
-                                float* d_gt_scale, float* d_gt_ori, void* hip_stream) {
-  if (const char* e = gt_arg_error(n_images, height, width)) return fail(HN_ERR_ARG, e);
-  if (n_images == 0) return HN_OK;
-  if (!d_ori || !d_homo12 || !d_homo21 || !d_gt_scale || !d_gt_ori)
-    return fail(HN_ERR_ARG, "NULL device pointer (only d_scale may be NULL)");
-  if ((reinterpret_cast<uintptr_t>(d_ori) | reinterpret_cast<uintptr_t>(d_gt_ori)) & 7)
-    return fail(HN_ERR_ARG, "d_ori and d_gt_ori must be 8-byte aligned");
-  HIPCHK(hn_launch_gt_scale_orin(d_scale, scale_value, d_ori, d_homo12, d_homo21, n_images, height, width, d_gt_scale,
-                                 d_gt_ori, static_cast<hipStream_t>(hip_stream)));
-  return HN_OK;
-}
-
-extern "C" int hn_mask_keypoints(const uint8_t* d_mask, int64_t n_images, int32_t height, int32_t width, int32_t topk,
-                                 const float* d_scale_map, float scale_value, const float* d_ori_map, int64_t* d_kpts,
-                                 float* d_kscale, float* d_kori, int32_t* d_counts, void* hip_stream) {
-  if (const char* e = gt_arg_error(n_images, height, width)) return fail(HN_ERR_ARG, e);
-  if (topk < 1 || topk > (int64_t)height * width) return fail(HN_ERR_ARG, "topk must be in 1 .. height * width");
-  if (n_images > INT64_MAX / 8 / topk) return fail(HN_ERR_ARG, "n_images * topk too large");
-  if ((d_kori == nullptr) != (d_ori_map == nullptr))
-    return fail(HN_ERR_ARG, "d_kori and d_ori_map must both be given or both NULL");
-  if (n_images == 0) return HN_OK;
-  if (!d_mask || !d_kpts || !d_kscale)
-    return fail(HN_ERR_ARG, "NULL device pointer (d_scale_map, d_ori_map / d_kori and d_counts may be)");
-  HIPCHK(hn_launch_mask_keypoints(d_mask, n_images, height, width, topk, d_scale_map, scale_value, d_ori_map, d_kpts,
-                                  d_kscale, d_kori, d_counts, static_cast<hipStream_t>(hip_stream)));
-  return HN_OK;
-}
-
-extern "C" int hn_project_keypoints(const int64_t* d_kpts, int64_t n, const float* d_homo, int64_t n_images,
-                                    int32_t height, int32_t width, const float* d_scale_map, float scale_value,
-                                    const float* d_ori_map, int32_t clamp, int64_t* d_kpts_r, float* d_scale_r,
-                                    float* d_ori_r, void* hip_stream) {
-  if (n < 0) return fail(HN_ERR_ARG, "n must be >= 0");
-  if (const char* e = gt_arg_error(n_images, height, width)) return fail(HN_ERR_ARG, e);
-  if (n > 0 && n_images == 0) return fail(HN_ERR_ARG, "n_images must be >= 1 for n > 0 keypoints");
-  if (clamp != 0 && clamp != 1) return fail(HN_ERR_ARG, "clamp must be 0 or 1");
-  if ((d_ori_r == nullptr) != (d_ori_map == nullptr))
-    return fail(HN_ERR_ARG, "d_ori_r and d_ori_map must both be given or both NULL");
-  if (n == 0) return HN_OK;
-  if (!d_kpts || !d_homo || !d_kpts_r || !d_scale_r)
-    return fail(HN_ERR_ARG, "NULL device pointer (d_scale_map and d_ori_map / d_ori_r may be)");
-  HIPCHK(hn_launch_project_kpts(d_kpts, n, d_homo, n_images, height, width, d_scale_map, scale_value, d_ori_map, clamp,
-                                d_kpts_r, d_scale_r, d_ori_r, static_cast<hipStream_t>(hip_stream)));
-  return HN_OK;
-}
-
-// ---------------------------------------------------------------------------------------
-// train-mode stock HardNet (hn_train.hip)
-// ---------------------------------------------------------------------------------------
-extern "C" int hn_hardnet_train_workspace_bytes(int64_t batch, size_t* saved_bytes_out, size_t* scratch_bytes_out) {
-  if (!saved_bytes_out || !scratch_bytes_out || batch < 2 || batch > (1 << 24))
-    return fail(HN_ERR_ARG, "batch must be 2 .. 2^24 (and both size pointers given)");
-  const HnTrainWs L = hn_train_layout((long)batch);
-  *saved_bytes_out = L.saved_total;
-  *scratch_bytes_out = L.scratch_total;
-  return HN_OK;
-}
-
-static int train_args(int64_t batch, const void* const* ptrs, int n, void* saved, size_t saved_bytes, void* scratch,
-                      size_t scratch_bytes) {
-  size_t need_sv = 0, need_sc = 0;
-  int rc = hn_hardnet_train_workspace_bytes(batch, &need_sv, &need_sc);
-  if (rc) return rc;
-  if (!saved || !scratch) return fail(HN_ERR_ARG, "NULL workspace");
-  if (saved_bytes < need_sv)
-    return fail(HN_ERR_WORKSPACE, "saved workspace too small: need " + std::to_string(need_sv) + " bytes");
-  if (scratch_bytes < need_sc)
-    return fail(HN_ERR_WORKSPACE, "scratch workspace too small: need " + std::to_string(need_sc) + " bytes");
-  if (!ptrs) return fail(HN_ERR_ARG, "NULL weight pointer array");
-  for (int i = 0; i < n; ++i)
-    if (!ptrs[i]) return fail(HN_ERR_ARG, "NULL weight pointer " + std::to_string(i));
-  return HN_OK;
-}
-
-extern "C" int hn_hardnet_train_forward(const float* d_in, int64_t batch, const float* const* d_weights,
-                                        float* const* d_running_mean, float* const* d_running_var, float momentum,
-                                        float dropout_p, uint64_t seed, float* d_out, void* d_saved,
-                                        size_t saved_bytes, void* d_scratch, size_t scratch_bytes,
-                                        void* hip_stream) {
-  int rc = train_args(batch, reinterpret_cast<const void* const*>(d_weights), 7, d_saved, saved_bytes, d_scratch,
-                      scratch_bytes);
-  if (rc) return rc;
-  if (!d_in || !d_out) return fail(HN_ERR_ARG, "NULL device pointer");
-  if ((d_running_mean == nullptr) != (d_running_var == nullptr))
-    return fail(HN_ERR_ARG, "running_mean and running_var must both be given or both NULL");
-  if (!(dropout_p >= 0.f && dropout_p < 1.f)) return fail(HN_ERR_ARG, "dropout_p must be in [0, 1)");
-  HIPCHK(hn_train_forward(d_in, (long)batch, d_weights, d_running_mean, d_running_var, momentum, 1e-5f, 1e-7f,
-                          1e-10f, dropout_p, (unsigned long long)seed, d_out, static_cast<char*>(d_saved),
-                          static_cast<char*>(d_scratch), static_cast<hipStream_t>(hip_stream)));
-  return HN_OK;
-}
-
-extern "C" int hn_hardnet_train_backward(const float* d_dout, int64_t batch, const float* const* d_weights,
-                                         float* const* d_dweights, float* d_din, float dropout_p, uint64_t seed,
-                                         void* d_saved, size_t saved_bytes, void* d_scratch, size_t scratch_bytes,
-                                         void* hip_stream) {
-  int rc = train_args(batch, reinterpret_cast<const void* const*>(d_weights), 7, d_saved, saved_bytes, d_scratch,
-                      scratch_bytes);
-  if (rc) return rc;
-  if (!d_dout) return fail(HN_ERR_ARG, "NULL device pointer");
-  if (!d_dweights) return fail(HN_ERR_ARG, "NULL gradient pointer array");
-  for (int i = 0; i < 7; ++i)
-    if (!d_dweights[i]) return fail(HN_ERR_ARG, "NULL gradient pointer " + std::to_string(i));
-  if (!(dropout_p >= 0.f && dropout_p < 1.f)) return fail(HN_ERR_ARG, "dropout_p must be in [0, 1)");
-  HIPCHK(hn_train_backward(d_dout, (long)batch, d_weights, d_dweights, d_din, 1e-10f, dropout_p,
-                           (unsigned long long)seed, static_cast<char*>(d_saved), static_cast<char*>(d_scratch),
-                           static_cast<hipStream_t>(hip_stream)));
-  return HN_OK;
-}
-
-// ---------------------------------------------------------------------------------------
-// train-mode hardnetNAS (hn_nas_train.hip)
-// ---------------------------------------------------------------------------------------
-static int nas_train_desc_ok(const hn_arch_desc* d) {
-  if (!d) return fail(HN_ERR_ARG, "NULL desc");
-  const bool fdl = d->kind == HN_KIND_FDL_NASNET || d->kind == HN_KIND_FDL_NASNET01;
-  if (d->kind != HN_KIND_NAS && d->kind != HN_KIND_NAS_SUPERNET && !fdl)
-    return fail(HN_ERR_ARG, "train mode: desc kind must be HN_KIND_NAS, HN_KIND_NAS_SUPERNET or an FDL kind");
-  if (d->n_layers < 1 || d->n_layers > HN_MAX_LAYERS) return fail(HN_ERR_ARG, "bad n_layers");
-  if (fdl && !(d->input_norm_eps >= 0.f)) return fail(HN_ERR_ARG, "FDL: input_norm_eps must be >= 0");
-  int hw = fdl ? 8 : 32, c = fdl ? 64 : 32;  // the FDL fronts leave 64 channels at 8x8
-  for (int i = 0; i < d->n_layers; ++i) {
-    if (d->kind != HN_KIND_NAS_SUPERNET && (d->op[i] < 0 || d->op[i] >= 17)) return fail(HN_ERR_ARG, "bad op index");
-    if (d->c_in[i] != c || (d->stride[i] != 1 && d->stride[i] != 2) || hw % d->stride[i])
-      return fail(HN_ERR_ARG, "layer " + std::to_string(i) + ": channels / stride do not chain");
-    if (d->c_out[i] < 1 || d->c_out[i] > 128 || d->c_in[i] % 4 || d->c_out[i] % 4)
-      return fail(HN_ERR_ARG, "layer " + std::to_string(i) + ": channel count");
-    c = d->c_out[i];
-    hw /= d->stride[i];
-  }
-  if (hw != 4) return fail(HN_ERR_ARG, "the layers must reduce the front's output to the 4x4 head input");
-  return HN_OK;
-}
-
-extern "C" int hn_nas_train_tensor_count(const hn_arch_desc* desc, size_t* n_out) {
-  int rc = nas_train_desc_ok(desc);
-  if (rc) return rc;
-  if (!n_out) return fail(HN_ERR_ARG, "NULL n_out");
-  hn_nas_train_plan(*desc, 2, n_out, nullptr, nullptr);
-  return HN_OK;
-}
-
-extern "C" int hn_nas_train_workspace_bytes(const hn_arch_desc* desc, int64_t batch, size_t* saved_bytes_out,
-                                            size_t* scratch_bytes_out) {
-  int rc = nas_train_desc_ok(desc);
-  if (rc) return rc;
-  if (!saved_bytes_out || !scratch_bytes_out || batch < 2 || batch > (1 << 22))
-    return fail(HN_ERR_ARG, "batch must be 2 .. 2^22 (and both size pointers given)");
-  hn_nas_train_plan(*desc, (long)batch, nullptr, saved_bytes_out, scratch_bytes_out);
-  return HN_OK;
-}
-
-static int nas_train_args(const hn_arch_desc* desc, int64_t batch, float* const* tensors, void* saved,
-                          size_t saved_bytes, void* scratch, size_t scratch_bytes, const float* soft) {
-  size_t need_sv = 0, need_sc = 0, nt = 0;
-  int rc = hn_nas_train_workspace_bytes(desc, batch, &need_sv, &need_sc);
-  if (rc) return rc;
-  hn_nas_train_plan(*desc, (long)batch, &nt, nullptr, nullptr);
-  if (!saved || !scratch) return fail(HN_ERR_ARG, "NULL workspace");
-  if (saved_bytes < need_sv)
-    return fail(HN_ERR_WORKSPACE, "saved workspace too small: need " + std::to_string(need_sv) + " bytes");
-  if (scratch_bytes < need_sc)
-    return fail(HN_ERR_WORKSPACE, "scratch workspace too small: need " + std::to_string(need_sc) + " bytes");
-  if (!tensors) return fail(HN_ERR_ARG, "NULL tensor pointer array");
-  for (size_t i = 0; i < nt; ++i)
-    if (!tensors[i]) return fail(HN_ERR_ARG, "NULL tensor pointer " + std::to_string(i));
-  if (desc->kind == HN_KIND_NAS_SUPERNET && !soft) return fail(HN_ERR_ARG, "the supernet needs d_soft");
-  return HN_OK;
-}
-
-extern "C" int hn_nas_train_forward(const hn_arch_desc* desc, const float* d_in, int64_t batch, float* const* d_tensors,
-                                    float momentum, const float* d_soft, float* d_out, void* d_saved,
-                                    size_t saved_bytes, void* d_scratch, size_t scratch_bytes, void* hip_stream) {
-  int rc = nas_train_args(desc, batch, d_tensors, d_saved, saved_bytes, d_scratch, scratch_bytes, d_soft);
-  if (rc) return rc;
-  if (!d_in || !d_out) return fail(HN_ERR_ARG, "NULL device pointer");
-  HIPCHK(hn_nas_train_forward_impl(*desc, d_in, (long)batch, d_tensors, momentum, d_soft, d_out,
-                                   static_cast<char*>(d_saved), static_cast<char*>(d_scratch),
-                                   static_cast<hipStream_t>(hip_stream)));
-  return HN_OK;
-}
-
-extern "C" int hn_nas_train_backward(const hn_arch_desc* desc, const float* d_dout, const float* d_in, int64_t batch,
-                                     float* const* d_tensors, const float* d_soft, float* const* d_grads,
-                                     float* d_dsoft, void* d_saved, size_t saved_bytes, void* d_scratch,
-                                     size_t scratch_bytes, void* hip_stream) {
-  return hn_nas_train_backward_dx(desc, d_dout, d_in, batch, d_tensors, d_soft, d_grads, d_dsoft, nullptr, d_saved,
-                                  saved_bytes, d_scratch, scratch_bytes, hip_stream);
-}
-
-extern "C" int hn_nas_train_backward_dx(const hn_arch_desc* desc, const float* d_dout, const float* d_in,
-                                        int64_t batch, float* const* d_tensors, const float* d_soft,
-                                        float* const* d_grads, float* d_dsoft, float* d_din, void* d_saved,
-                                        size_t saved_bytes, void* d_scratch, size_t scratch_bytes, void* hip_stream) {
-  int rc = nas_train_args(desc, batch, d_tensors, d_saved, saved_bytes, d_scratch, scratch_bytes, d_soft);
-  if (rc) return rc;
-  if (!d_dout || !d_in) return fail(HN_ERR_ARG, "NULL device pointer");
-  if (!d_grads) return fail(HN_ERR_ARG, "NULL gradient pointer array");
-  if (const int slot = hn_nas_train_null_grad_slot(*desc, d_grads); slot >= 0) {
-    return fail(HN_ERR_ARG, "d_grads[" + std::to_string(slot) + "] is NULL: every weight slot needs a gradient buffer");
-  }
-  if (desc->kind == HN_KIND_NAS_SUPERNET && !d_dsoft) return fail(HN_ERR_ARG, "the supernet needs d_dsoft");
-  if (reinterpret_cast<uintptr_t>(d_din) & 15) return fail(HN_ERR_ARG, "d_din must be 16-byte aligned");
-  HIPCHK(hn_nas_train_backward_impl(*desc, d_dout, (long)batch, d_in, d_tensors, d_soft, d_grads, d_dsoft, d_din,
-                                    static_cast<char*>(d_saved), static_cast<char*>(d_scratch),
-                                    static_cast<hipStream_t>(hip_stream)));
-  return HN_OK;
-}
-
-extern "C" int hn_hardnet_loss_train_workspace_bytes(int64_t batch, size_t* bytes_out) {
-  if (!bytes_out || batch < 1 || batch > (1 << 22)) return fail(HN_ERR_ARG, "batch out of range");
-  *bytes_out = hn_loss_train_saved_bytes((long)batch);
-  return HN_OK;
-}
-
-static int loss_train_args(const float* a, const float* p, int64_t batch, int32_t dim, int32_t loss_type,
-                           void* saved, size_t saved_bytes) {
-  if (!a || !p || !saved) return fail(HN_ERR_ARG, "NULL device pointer");
-  if (batch < 1 || batch > (1 << 22)) return fail(HN_ERR_ARG, "batch out of range");
-  if (dim != 128) return fail(HN_ERR_ARG, "dim must be 128");
-  if (loss_type < 0 || loss_type > 2) return fail(HN_ERR_ARG, "unknown loss_type");
-  if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(saved)) & 15)
-    return fail(HN_ERR_ARG, "device pointers must be 16-byte aligned");
-  if (saved_bytes < hn_loss_train_saved_bytes((long)batch)) return fail(HN_ERR_WORKSPACE, "saved workspace too small");
-  return HN_OK;
-}
-
-extern "C" int hn_hardnet_loss_train_forward(const float* d_anchor, const float* d_positive, int64_t batch,
-                                             int32_t dim, int32_t anchor_swap, float margin, int32_t loss_type,
-                                             float* d_loss, void* d_saved, size_t saved_bytes, void* hip_stream) {
-  if (int rc = loss_train_args(d_anchor, d_positive, batch, dim, loss_type, d_saved, saved_bytes)) return rc;
-  if (!d_loss) return fail(HN_ERR_ARG, "NULL device pointer");
-  HIPCHK(hn_launch_loss_train_fwd(d_anchor, d_positive, (int)batch, anchor_swap ? 1 : 0, margin, loss_type, d_loss,
-                                  d_saved, static_cast<hipStream_t>(hip_stream)));
-  return HN_OK;
-}
-
-extern "C" int hn_hardnet_loss_backward(const float* d_anchor, const float* d_positive, int64_t batch, int32_t dim,
-                                        int32_t anchor_swap, float margin, int32_t loss_type, const float* d_dloss,
-                                        float* d_grad_anchor, float* d_grad_positive, void* d_saved,
-                                        size_t saved_bytes, void* hip_stream) {
-  if (int rc = loss_train_args(d_anchor, d_positive, batch, dim, loss_type, d_saved, saved_bytes)) return rc;
-  if (!d_dloss || !d_grad_anchor || !d_grad_positive) return fail(HN_ERR_ARG, "NULL device pointer");
-  if ((reinterpret_cast<uintptr_t>(d_grad_anchor) | reinterpret_cast<uintptr_t>(d_grad_positive)) & 7)
-    return fail(HN_ERR_ARG, "gradient pointers must be 8-byte aligned");
-  HIPCHK(hn_launch_loss_train_bwd(d_anchor, d_positive, (int)batch, anchor_swap ? 1 : 0, margin, loss_type, d_dloss,
-                                  d_grad_anchor, d_grad_positive, d_saved, static_cast<hipStream_t>(hip_stream)));
-  return HN_OK;
-}
-
-extern "C" int hn_neimask_loss_workspace_bytes(int64_t batch, size_t* bytes_out) {
-  if (!bytes_out || batch < 1 || batch > (1 << 22)) return fail(HN_ERR_ARG, "batch out of range");
-  *bytes_out = hn_neimask_saved_bytes((long)batch);
-  return HN_OK;
-}
-
-static int neimask_args(const float* a, const float* p, int64_t batch, int32_t dim, void* saved, size_t saved_bytes) {
-  if (!a || !p || !saved) return fail(HN_ERR_ARG, "NULL device pointer");
-  if (batch < 1 || batch > (1 << 22)) return fail(HN_ERR_ARG, "batch out of range");
-  if (dim != 128) return fail(HN_ERR_ARG, "dim must be 128");
-  if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(saved)) & 15)
-    return fail(HN_ERR_ARG, "device pointers must be 16-byte aligned");
-  if (saved_bytes < hn_neimask_saved_bytes((long)batch)) return fail(HN_ERR_WORKSPACE, "saved workspace too small");
-  return HN_OK;
-}
-
-extern "C" int hn_neimask_loss_forward(const float* d_anchor, const float* d_positive, const int64_t* d_anchor_kp,
-                                       const int64_t* d_positive_kp, int64_t batch, int32_t dim, float margin,
-                                       float coo_thresh, float* d_loss, float* d_pos, float* d_min_neg, void* d_saved,
-                                       size_t saved_bytes, void* hip_stream) {
-  if (int rc = neimask_args(d_anchor, d_positive, batch, dim, d_saved, saved_bytes)) return rc;
-  if (!d_anchor_kp || !d_positive_kp || !d_loss) return fail(HN_ERR_ARG, "NULL device pointer");
-  if ((reinterpret_cast<uintptr_t>(d_anchor_kp) | reinterpret_cast<uintptr_t>(d_positive_kp)) & 7)
-    return fail(HN_ERR_ARG, "keypoint pointers must be 8-byte aligned");
-  if ((reinterpret_cast<uintptr_t>(d_loss) | reinterpret_cast<uintptr_t>(d_pos) | reinterpret_cast<uintptr_t>(d_min_neg)) & 3)
-    return fail(HN_ERR_ARG, "output pointers must be 4-byte aligned");
-  HIPCHK(hn_launch_neimask_fwd(d_anchor, d_positive, reinterpret_cast<const long long*>(d_anchor_kp),
-                               reinterpret_cast<const long long*>(d_positive_kp), (int)batch, margin, coo_thresh, d_loss,
-                               d_pos, d_min_neg, d_saved, static_cast<hipStream_t>(hip_stream)));
-  return HN_OK;
-}
-
-extern "C" int hn_neimask_loss_backward(const float* d_anchor, const float* d_positive, int64_t batch, int32_t dim,
-                                        float margin, const float* d_dloss, float* d_grad_anchor,
-                                        float* d_grad_positive, void* d_saved, size_t saved_bytes, void* hip_stream) {
-  if (int rc = neimask_args(d_anchor, d_positive, batch, dim, d_saved, saved_bytes)) return rc;
-  if (!d_dloss || !d_grad_anchor || !d_grad_positive) return fail(HN_ERR_ARG, "NULL device pointer");
-  if ((reinterpret_cast<uintptr_t>(d_grad_anchor) | reinterpret_cast<uintptr_t>(d_grad_positive)) & 7)
-    return fail(HN_ERR_ARG, "gradient pointers must be 8-byte aligned");
-  HIPCHK(hn_launch_neimask_bwd(d_anchor, d_positive, (int)batch, margin, d_dloss, d_grad_anchor, d_grad_positive,
-                               d_saved, static_cast<hipStream_t>(hip_stream)));
-  return HN_OK;
-}
-
-extern "C" int hn_pairdist_workspace_bytes(int64_t batch, size_t* bytes_out) {
-  if (!bytes_out || batch < 0) return fail(HN_ERR_ARG, "bad argument");
-  // column minima (padded to 64 entries) + the row kernel's workspace (hn_pairdist_rows_ws_bytes)
-  const long b = batch > 0 ? (long)batch : 1;
-  *bytes_out = (size_t)((b + 63) / 64 * 64) * sizeof(float) + hn_pairdist_rows_ws_bytes(b, b);
-  return HN_OK;
-}
-
-extern "C" int hn_pairdist_hardneg(const float* d_anchor, const float* d_positive, int64_t batch,
-                                   int32_t dim, int32_t anchor_swap, float* d_pos,
-                                   float* d_min_neg, void* d_workspace, size_t workspace_bytes,
-                                   void* hip_stream) {
-  if (!d_anchor || !d_positive || !d_pos || !d_min_neg || !d_workspace)
-    return fail(HN_ERR_ARG, "NULL device pointer");
-  if (batch < 2 || batch > (1 << 30)) return fail(HN_ERR_ARG, "batch out of range");
-  if (dim != 128) return fail(HN_ERR_ARG, "dim must be 128");
-  size_t need = 0;
-  hn_pairdist_workspace_bytes(batch, &need);
-  if (workspace_bytes < need) return fail(HN_ERR_WORKSPACE, "workspace too small");
-  HIPCHK(hn_launch_pairdist(d_anchor, d_positive, (int)batch, dim, anchor_swap, d_pos, d_min_neg,
-                            d_workspace, static_cast<hipStream_t>(hip_stream)));
-  return HN_OK;
-}
-
-extern "C" int hn_pairdist_rows_workspace_bytes(int64_t n_rows, int64_t batch, size_t* bytes_out) {
-  if (!bytes_out || n_rows < 1 || batch < 2 || batch > (1 << 30) || n_rows > batch)
-    return fail(HN_ERR_ARG, "bad n_rows / batch");
-  *bytes_out = hn_pairdist_rows_ws_bytes((long)n_rows, (long)batch);
-  return HN_OK;
-}
-
-extern "C" int hn_pairdist_rows(const float* d_anchor_rows, int64_t n_rows, int64_t row0,
-                                const float* d_positive, int64_t batch, int32_t dim, float* d_pos,
-                                float* d_row_min, float* d_col_min, void* d_workspace,
-                                size_t workspace_bytes, void* hip_stream) {
-  if (!d_anchor_rows || !d_positive || !d_pos || !d_row_min || !d_workspace)
-    return fail(HN_ERR_ARG, "NULL device pointer");
-  if (dim != 128) return fail(HN_ERR_ARG, "dim must be 128");
-  size_t need = 0;
-  int rc = hn_pairdist_rows_workspace_bytes(n_rows, batch, &need);
-  if (rc) return rc;
-  if (row0 < 0 || row0 + n_rows > batch) return fail(HN_ERR_ARG, "rows [row0, row0 + n_rows) outside the batch");
-  if (workspace_bytes < need) return fail(HN_ERR_WORKSPACE, "workspace too small");
-  if ((reinterpret_cast<uintptr_t>(d_anchor_rows) | reinterpret_cast<uintptr_t>(d_positive)) & 15)
-    return fail(HN_ERR_ARG, "descriptor pointers must be 16-byte aligned");
-  HIPCHK(hn_launch_pairdist_rows(d_anchor_rows, (int)n_rows, (int)row0, d_positive, (int)batch, d_pos,
-                                 d_row_min, d_col_min, d_workspace, static_cast<hipStream_t>(hip_stream)));
-  return HN_OK;
-}
-
-static const char* match_size_error(int64_t n_query, int64_t n_db) {
-  if (n_query < 1 || n_query > (1 << 22)) return "n_query must be 1 .. 2^22";
-  if (n_db < 1 || n_db > (1 << 22)) return "n_db must be 1 .. 2^22";
-  return nullptr;
-}
-
-extern "C" int hn_match_workspace_bytes(int64_t n_query, int64_t n_db, size_t* bytes_out) {
-  if (!bytes_out) return fail(HN_ERR_ARG, "bytes_out is NULL");
-  if (const char* e = match_size_error(n_query, n_db)) return fail(HN_ERR_ARG, e);
-  *bytes_out = hn_match_ws_bytes((long)n_query, (long)n_db);
-  return HN_OK;
-}
-
-extern "C" int hn_match_nn2(const float* d_query, int64_t n_query, const float* d_db, int64_t n_db, int32_t dim,
-                            int32_t metric, float* d_dist, int32_t* d_idx, void* d_workspace,
-                            size_t workspace_bytes, void* hip_stream) {
-  if (dim != 128) return fail(HN_ERR_ARG, "dim must be 128, got " + std::to_string(dim));
-  if (metric != HN_METRIC_UNIT && metric != HN_METRIC_L2)
-    return fail(HN_ERR_ARG, "unknown metric " + std::to_string(metric) + " (HN_METRIC_UNIT, HN_METRIC_L2)");
-  if (const char* e = match_size_error(n_query, n_db)) return fail(HN_ERR_ARG, e);
-  const size_t need = hn_match_ws_bytes((long)n_query, (long)n_db);
-  if (workspace_bytes < need)
-    return fail(HN_ERR_WORKSPACE, "workspace too small: need " + std::to_string(need) + " bytes");
-  if (!d_query || !d_db || !d_dist || !d_idx || !d_workspace) return fail(HN_ERR_ARG, "NULL device pointer");
-  if ((reinterpret_cast<uintptr_t>(d_query) | reinterpret_cast<uintptr_t>(d_db) |
-       reinterpret_cast<uintptr_t>(d_workspace)) & 15)
-    return fail(HN_ERR_ARG, "d_query / d_db / d_workspace must be 16-byte aligned");
-  if ((reinterpret_cast<uintptr_t>(d_dist) | reinterpret_cast<uintptr_t>(d_idx)) & 7)
-    return fail(HN_ERR_ARG, "d_dist / d_idx must be 8-byte aligned");
-  HIPCHK(hn_launch_match_nn2(d_query, (int)n_query, d_db, (int)n_db, metric, d_dist, d_idx, d_workspace,
-                             static_cast<hipStream_t>(hip_stream)));
-  return HN_OK;
-}
-
-extern "C" int hn_hardnet_loss(const float* d_pos, const float* d_row_min, const float* d_col_min,
-                               int64_t n, float margin, int32_t loss_type, float scale,
-                               float* d_min_neg, float* d_loss, void* hip_stream) {
-  if (!d_pos || !d_row_min || !d_loss) return fail(HN_ERR_ARG, "NULL device pointer");
-  if (n < 1 || n > (1 << 30)) return fail(HN_ERR_ARG, "n out of range");
-  if (loss_type < HN_LOSS_TRIPLET_MARGIN || loss_type > HN_LOSS_CONTRASTIVE)
-    return fail(HN_ERR_ARG, "unknown loss_type " + std::to_string(loss_type) +
-                                " (Losses.py:142-152: triplet_margin, softmax, contrastive)");
-  HIPCHK(hn_launch_loss(d_pos, d_row_min, d_col_min, (int)n, margin, loss_type, scale, d_min_neg, d_loss,
-                        static_cast<hipStream_t>(hip_stream)));
-  return HN_OK;
-}
-
-extern "C" int hn_fpr95_workspace_bytes(int64_t n, size_t* bytes_out) {
-  if (!bytes_out || n < 1 || n > (int64_t)1 << 30) return fail(HN_ERR_ARG, "n out of range");
-  HIPCHK(hn_fpr95_ws_bytes(n, bytes_out));
-  return HN_OK;
-}
-
-extern "C" int hn_fpr95(const float* d_anchor, const float* d_positive, const int32_t* d_labels,
-                        int64_t n, int32_t dim, float* d_dists, double* d_fpr, void* d_workspace,
-                        size_t workspace_bytes, void* hip_stream) {
-  if (!d_anchor || !d_positive || !d_labels || !d_fpr || !d_workspace)
-    return fail(HN_ERR_ARG, "NULL device pointer");
-  if (n < 1 || n > (int64_t)1 << 30 || dim < 1) return fail(HN_ERR_ARG, "bad n / dim");
-  size_t need = 0;
-  HIPCHK(hn_fpr95_ws_bytes(n, &need));
-  if (workspace_bytes < need) return fail(HN_ERR_WORKSPACE, "workspace too small");
-  HIPCHK(hn_launch_fpr95(d_anchor, d_positive, d_labels, n, dim, d_dists, d_fpr, d_workspace,
-                         workspace_bytes, static_cast<hipStream_t>(hip_stream)));
-  return HN_OK;
-}
-
-extern "C" int hn_preprocess(const uint8_t* d_in, int64_t n, int32_t in_hw, int32_t resize,
-                             int32_t normalize, float mean, float stdv, float* d_out,
-                             void* hip_stream) {
-  if (n < 0) return fail(HN_ERR_ARG, "n < 0");
-  if (resize != HN_RESIZE_NONE && resize != HN_RESIZE_CV2_LINEAR && resize != HN_RESIZE_PIL_BILINEAR)
-    return fail(HN_ERR_ARG, "unknown resize mode " + std::to_string(resize));
-  const int want = resize == HN_RESIZE_NONE ? 32 : 64;
-  if (in_hw != want)
-    return fail(HN_ERR_ARG, "in_hw must be " + std::to_string(want) + " for this resize mode, got " +
-                                std::to_string(in_hw));
-  if (n == 0) return HN_OK;
-  if (!d_in || !d_out) return fail(HN_ERR_ARG, "NULL device pointer");
-  if ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out)) & 15)
-    return fail(HN_ERR_ARG, "d_in / d_out must be 16-byte aligned");
-  if (normalize && !(stdv != 0.0f)) return fail(HN_ERR_ARG, "std must be nonzero");
-  HIPCHK(hn_launch_preprocess(d_in, n, resize, normalize, mean, stdv, d_out,
-                              static_cast<hipStream_t>(hip_stream)));
   return HN_OK;
 }
 

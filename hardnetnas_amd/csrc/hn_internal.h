@@ -1,4 +1,4 @@
-// Internal host-side interface between the C ABI (hn_api.hip) and the kernel files.
+// Internal host-side interface between the C ABI (hn_api*.hip; their own helpers: hn_api_util.h) and the kernel files.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,7 +1,7 @@
 """fp16 range of the NAS / FDL fp16x3 kernels.
 
 The hi half of an fp16x3 operand overflows at |v| >= 65520.  BN-folded weights out of range
-make hn_create fail (csrc/hn_api.hip put_f16_split); activations are data-dependent, so
+make hn_create fail (csrc/hn_pack.h put_f16_split); activations are data-dependent, so
 hardnetnas_amd.model.fp16_split_margin measures them on a calibration batch with the module's
 torch layers.  These tests pin both, and check that large-but-in-range activations keep parity.
 """
