@@ -413,16 +413,7 @@ def test_nas_unfused_front_matches(name, cuda_device, monkeypatch):
     assert np.abs(y - fx["y"]).max() <= NAS_TOL
 
 
-def _synth_nas(ops, seed=99):
-    from hardnetnas_amd import synth
-    from hardnetnas_amd.model import HardNetNAS
-    m = HardNetNAS(list(ops))
-    sd = m.state_dict()
-    w = synth.synth_state_dict({k: tuple(v.shape) for k, v in sd.items()}, seed)
-    for k in w:
-        sd[k] = torch.from_numpy(w[k])
-    m.load_state_dict(sd)
-    return m.eval(), {k: torch.from_numpy(v) for k, v in w.items()}
+from nas_arch_cases import _synth_nas  # noqa: E402  (the synthetic-weight NAS builder, shared with the arch sets)
 
 
 @pytest.mark.parametrize("op", ["skip", "ir_k3_e1", "ir_k3_e3", "ir_k3_s4", "ir_k5_e1", "ir_k5_e3",
