@@ -486,6 +486,18 @@ class HardNetLossFunction(torch.autograd.Function):
         return ga, gp, None, None, None
 
 
+def hardnet_loss_saved_argmins(saved: torch.Tensor, b: int):
+    """(row argmin [b], column argmin [b]) int64 out of the workspace ``HardNetLossFunction`` saves for its
+    backward (``loss.grad_fn.saved_tensors[2]``; the layout above hn_loss_train_saved_bytes in hn_loss.hip:
+    sq [2b] f32, then rowbest [b] u64 and colbest [b] u64 -- value bits << 32 | argmin --, each block 256-byte
+    aligned).  Read-only.  The column block is written only by a forward with anchor_swap."""
+    def al(n):
+        return (n + 255) // 256 * 256
+    o, blk = al(8 * b), al(8 * b)  # (2b floats take 8b bytes)
+    keys = saved[o:o + 2 * blk].view(torch.int64)
+    return keys[:b] & 0xffffffff, keys[blk // 8:blk // 8 + b] & 0xffffffff
+
+
 def _aligned16(x: torch.Tensor) -> torch.Tensor:
     """A contiguous, detached x whose rows the C ABI can take (16-byte aligned: a contiguous view at an odd
     storage offset is copied)."""

@@ -207,10 +207,21 @@ __global__ __launch_bounds__(256) void k_lmin_bwd_src(const float* __restrict__ 
   const int c = swap ? key_idx(colbest[i]) : 0;
   const float gp = g * dp, gn = g * dm;
   // the positive entry: sqrt's backward at the forward's own |a_i - p_i|^2 (k_lmin_sq's difference form)
-  const float cp = gp != 0.f ? gp * (0.5f / sqrtf(posx[i] + 1e-6f)) : 0.f;
-  coef[3 * i + 0] = cp;
-  coef[3 * i + 1] = gn * fr != 0.f ? gn * fr * half_rsq(a, p, sq, B, i, r) : 0.f;
-  coef[3 * i + 2] = gn * (1.f - fr) != 0.f ? gn * (1.f - fr) * half_rsq(a, p, sq, B, c, i) : 0.f;
+  float wp = gp, w1 = gn * fr, w2 = gn * (1.f - fr);
+  // a selected negative that is the row's own masked diagonal (B = 1, or every other entry beyond d_ii + 10) is
+  // the positive's entry (i, i): its weight joins the positive's before sqrt's backward, as autograd accumulates
+  // the two on d_ii -- the clamp losses' +g and -g then cancel to exactly zero, as there
+  if (r == i) {
+    wp += w1;
+    w1 = 0.f;
+  }
+  if (swap && c == i) {
+    wp += w2;
+    w2 = 0.f;
+  }
+  coef[3 * i + 0] = wp != 0.f ? wp * (0.5f / sqrtf(posx[i] + 1e-6f)) : 0.f;
+  coef[3 * i + 1] = w1 != 0.f ? w1 * half_rsq(a, p, sq, B, i, r) : 0.f;
+  coef[3 * i + 2] = w2 != 0.f ? w2 * half_rsq(a, p, sq, B, c, i) : 0.f;
   idx[2 * i + 0] = r;
   idx[2 * i + 1] = c;
 }

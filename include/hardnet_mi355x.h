@@ -214,7 +214,9 @@ int hn_neimask_loss_backward(const float* d_anchor, const float* d_positive, int
  * first index reaching 95 % recall, FP / (FP + TN).
  * d_anchor, d_positive: [n,dim] fp32; d_labels: [n] int32 (1 = match).  Outputs: d_dists
  * ([n] fp32 pair distances, may be NULL) and d_fpr (one double; NaN if there are no
- * negatives).  Ties are ordered stably (numpy's quicksort order is unspecified). */
+ * negatives; 0 if there are no matches).  Ties are ordered stably (numpy's quicksort order is
+ * unspecified).  Labels: any nonzero value counts as one match, 0 as a non-match; the reference's
+ * cumsum adds the labels raw, so it agrees only for labels in {0, 1}. */
 int hn_fpr95_workspace_bytes(int64_t n, size_t* bytes_out);
 int hn_fpr95(const float* d_anchor, const float* d_positive, const int32_t* d_labels, int64_t n,
              int32_t dim, float* d_dists, double* d_fpr, void* d_workspace, size_t workspace_bytes,
