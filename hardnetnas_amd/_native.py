@@ -5,6 +5,10 @@ the caching allocator) and the current HIP stream; all arithmetic of the forward
 in the library's gfx950 kernels.  ``torch`` is imported before the library is loaded so
 that both share the one HIP runtime already mapped by torch (SONAME libamdhip64.so.7).
 
+The module is a prototype table (``_PROTOTYPES``, one row per ABI function), a handful of call
+helpers (``_call``, ``_size``, ``_workspace``, ``_out``, ...) and the wrappers over them: a new
+entry point is one table row plus the lines that are specific to its wrapper.
+
 There is no fallback: if the library cannot be loaded, every entry point raises.
 """
 from __future__ import annotations
@@ -25,13 +29,18 @@ _LIB_NAME = "libhardnet_mi355x.so"
 _lib = None
 _lib_lock = threading.Lock()
 
+# mirrors of the header's constants (tests/test_native_binding.py compares them with the header)
 HN_KIND_HARDNET = 0
 HN_KIND_NAS = 1
 HN_KIND_FDL_NASNET = 2
 HN_KIND_FDL_NASNET01 = 3
 HN_KIND_NAS_SUPERNET = 4  # train mode only (hn_nas_train_*)
 HN_MAX_LAYERS = 8
-ABI_VERSION = 2   # HN_ABI_VERSION of include/hardnet_mi355x.h
+ABI_VERSION = 2   # HN_ABI_VERSION
+DET_TRAIN_TENSORS = 40  # HN_DET_TRAIN_TENSORS
+LOSS_TYPES = {"triplet_margin": 0, "softmax": 1, "contrastive": 2}  # enum hn_loss_type
+MATCH_METRICS = {"unit": 0, "l2": 1}  # enum hn_metric
+RESIZE_MODES = {"none": 0, "cv2": 1, "pil": 2}  # enum hn_resize
 
 
 class HnArchDesc(ctypes.Structure):
@@ -48,33 +57,91 @@ class HnArchDesc(ctypes.Structure):
     ]
 
 
-EXPORTED = ["hn_param_count", "hn_create", "hn_workspace_bytes", "hn_forward",
-            "hn_pairdist_workspace_bytes", "hn_pairdist_hardneg", "hn_pairdist_rows_workspace_bytes",
-            "hn_pairdist_rows", "hn_hardnet_loss", "hn_workspace_bytes_u8", "hn_forward_u8",
-            "hn_hardnet_train_workspace_bytes", "hn_hardnet_train_forward", "hn_hardnet_train_backward",
-            "hn_nas_train_tensor_count", "hn_nas_train_workspace_bytes", "hn_nas_train_forward",
-            "hn_nas_train_backward", "hn_nas_train_backward_dx", "hn_hardnet_loss_train_workspace_bytes",
-            "hn_hardnet_loss_train_forward", "hn_hardnet_loss_backward",
-            "hn_neimask_loss_workspace_bytes", "hn_neimask_loss_forward",
-            "hn_neimask_loss_backward", "hn_fpr95_workspace_bytes",
-            "hn_fpr95", "hn_match_workspace_bytes", "hn_match_nn2", "hn_clip_patch", "hn_clip_patch_backward",
-            "hn_workspace_bytes_kp",
-            "hn_forward_kp", "hn_det_param_count", "hn_det_create", "hn_det_workspace_bytes", "hn_det_forward",
-            "hn_det_destroy", "hn_det_train_workspace_bytes", "hn_det_train_forward", "hn_det_train_backward",
-            "hn_select_workspace_bytes", "hn_select_keypoints", "hn_warp_score", "hn_gt_scale_orin",
-            "hn_mask_keypoints", "hn_project_keypoints", "hn_preprocess", "hn_set_profiling",
-            "hn_stage_times", "hn_destroy", "hn_last_error", "hn_abi_version"]
+# ----------------------------------------------------------------------------------
+# the prototype table: every ABI function and its argtypes, by subsystem in the header's order
+# ----------------------------------------------------------------------------------
+P, S, I32, I64, U64, F32 = (ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64,
+                            ctypes.c_float)
+SP, PP, D = ctypes.POINTER(S), ctypes.POINTER(P), ctypes.POINTER(HnArchDesc)  # size_t*, pointer array, descriptor
+
+_PROTOTYPES = {
+    # model and eval forward
+    "hn_param_count": (D, SP),
+    "hn_create": (D, P, S, PP),
+    "hn_workspace_bytes": (P, I64, SP),
+    "hn_forward": (P, P, I64, P, P, S, P),
+    # hardest-in-batch distances and loss_HardNet
+    "hn_pairdist_workspace_bytes": (I64, SP),
+    "hn_pairdist_hardneg": (P, P, I64, I32, I32, P, P, P, S, P),
+    "hn_pairdist_rows_workspace_bytes": (I64, I64, SP),
+    "hn_pairdist_rows": (P, I64, I64, P, I64, I32, P, P, P, P, S, P),
+    "hn_hardnet_loss": (P, P, P, I64, F32, I32, F32, P, P, P),
+    "hn_hardnet_loss_train_workspace_bytes": (I64, SP),
+    "hn_hardnet_loss_train_forward": (P, P, I64, I32, I32, F32, I32, P, P, S, P),
+    "hn_hardnet_loss_backward": (P, P, I64, I32, I32, F32, I32, P, P, P, P, S, P),
+    # FDLNet's neighbour-mask loss
+    "hn_neimask_loss_workspace_bytes": (I64, SP),
+    "hn_neimask_loss_forward": (P, P, P, P, I64, I32, F32, F32, P, P, P, P, S, P),
+    "hn_neimask_loss_backward": (P, P, I64, I32, F32, P, P, P, P, S, P),
+    # evaluation: FPR95, matching
+    "hn_fpr95_workspace_bytes": (I64, SP),
+    "hn_fpr95": (P, P, P, I64, I32, P, P, P, S, P),
+    "hn_match_workspace_bytes": (I64, I64, SP),
+    "hn_match_nn2": (P, I64, P, I64, I32, I32, P, P, P, S, P),
+    # uint8 patches
+    "hn_preprocess": (P, I64, I32, I32, I32, F32, F32, P, P),
+    "hn_workspace_bytes_u8": (P, I64, SP),
+    "hn_forward_u8": (P, P, I64, I32, I32, I32, F32, F32, P, P, S, P),
+    # keypoints to patches
+    "hn_clip_patch": (P, I64, I32, I32, P, P, P, P, I64, P, P),
+    "hn_clip_patch_backward": (P, P, I64, I32, I32, P, P, P, P, I64, P, P, P),
+    "hn_workspace_bytes_kp": (P, I64, SP),
+    "hn_forward_kp": (P, P, I64, I32, I32, P, P, P, P, I64, P, P, S, P),
+    # keypoint detector: eval, train, selection
+    "hn_det_param_count": (SP,),
+    "hn_det_create": (P, S, F32, F32, PP),
+    "hn_det_workspace_bytes": (I64, I32, I32, SP),
+    "hn_det_forward": (P, P, I64, I32, I32, P, P, P, S, P),
+    "hn_det_destroy": (P,),
+    "hn_det_train_workspace_bytes": (I64, I32, I32, SP, SP),
+    "hn_det_train_forward": (P, I64, I32, I32, PP, F32, F32, F32, P, P, P, S, P, S, P),
+    "hn_det_train_backward": (P, P, P, I64, I32, I32, PP, PP, P, S, P, S, P),
+    "hn_select_workspace_bytes": (I64, I32, I32, I32, SP),
+    "hn_select_keypoints": (P, I64, I32, I32, I32, F32, I32, I32, I32, F32, P, F32, P, P, P, P, P, P, P, P, S, P),
+    # homography ground-truth stage
+    "hn_warp_score": (P, P, I64, I32, I32, I32, I32, P, P, P),
+    "hn_gt_scale_orin": (P, F32, P, P, P, I64, I32, I32, P, P, P),
+    "hn_mask_keypoints": (P, I64, I32, I32, I32, P, F32, P, P, P, P, P, P),
+    "hn_project_keypoints": (P, I64, P, I64, I32, I32, P, F32, P, I32, P, P, P, P),
+    # train mode: stock HardNet, hardnetNAS / supernet / FDLNet
+    "hn_hardnet_train_workspace_bytes": (I64, SP, SP),
+    "hn_hardnet_train_forward": (P, I64, PP, PP, PP, F32, F32, U64, P, P, S, P, S, P),
+    "hn_hardnet_train_backward": (P, I64, PP, PP, P, F32, U64, P, S, P, S, P),
+    "hn_nas_train_tensor_count": (D, SP),
+    "hn_nas_train_workspace_bytes": (D, I64, SP, SP),
+    "hn_nas_train_forward": (D, P, I64, PP, F32, P, P, P, S, P, S, P),
+    "hn_nas_train_backward": (D, P, P, I64, PP, P, PP, P, P, S, P, S, P),
+    "hn_nas_train_backward_dx": (D, P, P, I64, PP, P, PP, P, P, P, S, P, S, P),
+    # profiling, lifetime, errors
+    "hn_set_profiling": (P, ctypes.c_int),
+    "hn_stage_times": (P, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_double),
+                       ctypes.POINTER(I64)),
+    "hn_destroy": (P,),
+    "hn_last_error": (),
+    "hn_abi_version": (),
+}
+# every function returns int (ctypes' default restype) but these
+_RESTYPES = {"hn_det_destroy": None, "hn_destroy": None, "hn_last_error": ctypes.c_char_p}
+EXPORTED = list(_PROTOTYPES)
 
 
 def lib_path() -> str:
-    env = os.environ.get("HN_LIB")
-    if env:
-        return env
-    return os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", _LIB_NAME)
+    return os.environ.get("HN_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", _LIB_NAME)
 
 
 def load_library():
-    """Load (once) and type the C ABI.  Raises if the library is missing."""
+    """Load (once) and type the C ABI.  Raises if the library is missing, or lacks a function of the table
+    (ctypes' AttributeError names the symbol)."""
     global _lib
     with _lib_lock:
         if _lib is not None:
@@ -85,120 +152,118 @@ def load_library():
                 f"hardnetnas_amd native library not found at {path}; build it with "
                 "`python -c 'import __graft_entry__ as g; g.build()'` (make -C hardnetnas_amd/csrc)")
         lib = ctypes.CDLL(path)
-        P, S, I32, I64 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int32, ctypes.c_int64
-        lib.hn_param_count.argtypes = [ctypes.POINTER(HnArchDesc), ctypes.POINTER(S)]
-        lib.hn_create.argtypes = [ctypes.POINTER(HnArchDesc), P, S, ctypes.POINTER(P)]
-        lib.hn_workspace_bytes.argtypes = [P, I64, ctypes.POINTER(S)]
-        lib.hn_forward.argtypes = [P, P, I64, P, P, S, P]
-        lib.hn_workspace_bytes_u8.argtypes = [P, I64, ctypes.POINTER(S)]
-        PP = ctypes.POINTER(P)
-        lib.hn_hardnet_train_workspace_bytes.argtypes = [I64, ctypes.POINTER(S), ctypes.POINTER(S)]
-        lib.hn_hardnet_train_forward.argtypes = [P, I64, PP, PP, PP, ctypes.c_float, ctypes.c_float,
-                                                 ctypes.c_uint64, P, P, S, P, S, P]
-        lib.hn_hardnet_train_backward.argtypes = [P, I64, PP, PP, P, ctypes.c_float, ctypes.c_uint64, P, S, P, S, P]
-        lib.hn_forward_u8.argtypes = [P, P, I64, I32, I32, I32, ctypes.c_float, ctypes.c_float, P, P, S, P]
-        D = ctypes.POINTER(HnArchDesc)
-        lib.hn_nas_train_tensor_count.argtypes = [D, ctypes.POINTER(S)]
-        lib.hn_nas_train_workspace_bytes.argtypes = [D, I64, ctypes.POINTER(S), ctypes.POINTER(S)]
-        lib.hn_nas_train_forward.argtypes = [D, P, I64, PP, ctypes.c_float, P, P, P, S, P, S, P]
-        lib.hn_nas_train_backward.argtypes = [D, P, P, I64, PP, P, PP, P, P, S, P, S, P]
-        lib.hn_nas_train_backward_dx.argtypes = [D, P, P, I64, PP, P, PP, P, P, P, S, P, S, P]
-        lib.hn_pairdist_workspace_bytes.argtypes = [I64, ctypes.POINTER(S)]
-        lib.hn_pairdist_hardneg.argtypes = [P, P, I64, I32, I32, P, P, P, S, P]
-        lib.hn_pairdist_rows_workspace_bytes.argtypes = [I64, I64, ctypes.POINTER(S)]
-        lib.hn_pairdist_rows.argtypes = [P, I64, I64, P, I64, I32, P, P, P, P, S, P]
-        lib.hn_hardnet_loss.argtypes = [P, P, P, I64, ctypes.c_float, I32, ctypes.c_float, P, P, P]
-        lib.hn_hardnet_loss_train_workspace_bytes.argtypes = [I64, ctypes.POINTER(S)]
-        lib.hn_hardnet_loss_train_forward.argtypes = [P, P, I64, I32, I32, ctypes.c_float, I32, P, P, S, P]
-        lib.hn_hardnet_loss_backward.argtypes = [P, P, I64, I32, I32, ctypes.c_float, I32, P, P, P, P, S, P]
-        lib.hn_neimask_loss_workspace_bytes.argtypes = [I64, ctypes.POINTER(S)]
-        lib.hn_neimask_loss_forward.argtypes = [P, P, P, P, I64, I32, ctypes.c_float, ctypes.c_float, P, P, P, P, S, P]
-        lib.hn_neimask_loss_backward.argtypes = [P, P, I64, I32, ctypes.c_float, P, P, P, P, S, P]
-        lib.hn_fpr95_workspace_bytes.argtypes = [I64, ctypes.POINTER(S)]
-        lib.hn_fpr95.argtypes = [P, P, P, I64, I32, P, P, P, S, P]
-        lib.hn_match_workspace_bytes.argtypes = [I64, I64, ctypes.POINTER(S)]
-        lib.hn_match_nn2.argtypes = [P, I64, P, I64, I32, I32, P, P, P, S, P]
-        lib.hn_clip_patch.argtypes = [P, I64, I32, I32, P, P, P, P, I64, P, P]
-        lib.hn_clip_patch_backward.argtypes = [P, P, I64, I32, I32, P, P, P, P, I64, P, P, P]
-        lib.hn_workspace_bytes_kp.argtypes = [P, I64, ctypes.POINTER(S)]
-        lib.hn_forward_kp.argtypes = [P, P, I64, I32, I32, P, P, P, P, I64, P, P, S, P]
-        F32 = ctypes.c_float
-        lib.hn_det_param_count.argtypes = [ctypes.POINTER(S)]
-        lib.hn_det_create.argtypes = [P, S, F32, F32, ctypes.POINTER(P)]
-        lib.hn_det_workspace_bytes.argtypes = [I64, I32, I32, ctypes.POINTER(S)]
-        lib.hn_det_forward.argtypes = [P, P, I64, I32, I32, P, P, P, S, P]
-        lib.hn_det_destroy.argtypes = [P]
-        lib.hn_det_destroy.restype = None
-        lib.hn_det_train_workspace_bytes.argtypes = [I64, I32, I32, ctypes.POINTER(S), ctypes.POINTER(S)]
-        lib.hn_det_train_forward.argtypes = [P, I64, I32, I32, PP, F32, F32, F32, P, P, P, S, P, S, P]
-        lib.hn_det_train_backward.argtypes = [P, P, P, I64, I32, I32, PP, PP, P, S, P, S, P]
-        lib.hn_select_workspace_bytes.argtypes = [I64, I32, I32, I32, ctypes.POINTER(S)]
-        lib.hn_select_keypoints.argtypes = [P, I64, I32, I32, I32, F32, I32, I32, I32, F32, P, F32, P, P, P, P, P, P, P,
-                                            P, S, P]
-        lib.hn_warp_score.argtypes = [P, P, I64, I32, I32, I32, I32, P, P, P]
-        lib.hn_gt_scale_orin.argtypes = [P, F32, P, P, P, I64, I32, I32, P, P, P]
-        lib.hn_mask_keypoints.argtypes = [P, I64, I32, I32, I32, P, F32, P, P, P, P, P, P]
-        lib.hn_project_keypoints.argtypes = [P, I64, P, I64, I32, I32, P, F32, P, I32, P, P, P, P]
-        lib.hn_preprocess.argtypes = [P, I64, I32, I32, I32, ctypes.c_float, ctypes.c_float, P, P]
-        lib.hn_set_profiling.argtypes = [P, ctypes.c_int]
-        lib.hn_stage_times.argtypes = [P, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p),
-                                       ctypes.POINTER(ctypes.c_double), ctypes.POINTER(I64)]
-        lib.hn_destroy.argtypes = [P]
-        lib.hn_destroy.restype = None
-        lib.hn_last_error.restype = ctypes.c_char_p
-        for name in ("hn_param_count", "hn_create", "hn_workspace_bytes", "hn_forward",
-                     "hn_pairdist_workspace_bytes", "hn_pairdist_hardneg", "hn_abi_version",
-                     "hn_set_profiling", "hn_stage_times", "hn_fpr95_workspace_bytes",
-                     "hn_fpr95", "hn_pairdist_rows_workspace_bytes", "hn_pairdist_rows",
-                     "hn_hardnet_loss", "hn_workspace_bytes_u8", "hn_forward_u8",
-                     "hn_hardnet_train_workspace_bytes", "hn_hardnet_train_forward",
-                     "hn_hardnet_train_backward", "hn_nas_train_tensor_count", "hn_nas_train_workspace_bytes",
-                     "hn_nas_train_forward", "hn_nas_train_backward", "hn_hardnet_loss_train_workspace_bytes",
-                     "hn_hardnet_loss_train_forward", "hn_hardnet_loss_backward", "hn_neimask_loss_workspace_bytes",
-                     "hn_neimask_loss_forward", "hn_neimask_loss_backward", "hn_match_workspace_bytes",
-                     "hn_match_nn2", "hn_clip_patch", "hn_workspace_bytes_kp", "hn_forward_kp",
-                     "hn_clip_patch_backward", "hn_nas_train_backward_dx",
-                     "hn_det_param_count", "hn_det_create", "hn_det_workspace_bytes", "hn_det_forward",
-                     "hn_select_workspace_bytes", "hn_select_keypoints", "hn_warp_score", "hn_gt_scale_orin",
-                     "hn_mask_keypoints", "hn_project_keypoints", "hn_det_train_workspace_bytes",
-                     "hn_det_train_forward", "hn_det_train_backward"):
-            getattr(lib, name).restype = ctypes.c_int
+        for name, argtypes in _PROTOTYPES.items():
+            fn = getattr(lib, name)
+            fn.argtypes = list(argtypes)
+            if name in _RESTYPES:
+                fn.restype = _RESTYPES[name]
         if lib.hn_abi_version() != ABI_VERSION:
             raise RuntimeError(f"{path}: ABI version {lib.hn_abi_version()}, expected {ABI_VERSION}; rebuild it")
         _lib = lib
         return lib
 
 
+# ----------------------------------------------------------------------------------
+# call helpers
+# ----------------------------------------------------------------------------------
 def _check(rc: int, what: str):
     if rc != 0:
         msg = load_library().hn_last_error().decode(errors="replace")
         raise RuntimeError(f"{what} failed (status {rc}): {msg}")
 
 
+def _call(dev, name: str, *args):
+    """Launch ABI function ``name`` on the current stream of ``dev`` (appended as the last argument) with ``dev``
+    the current device, and check its status.  A tensor argument is passed as its data pointer, None as NULL,
+    anything else as it is.  Nothing here synchronises: the call stays capturable."""
+    fn = getattr(_lib or load_library(), name)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        _check(fn(*[a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args], stream), name)
+
+
+def _size(name: str, *args, n: int = 1):
+    """The ``n`` trailing size_t outputs of a ``*_workspace_bytes`` / ``*_count`` function: an int, or a tuple
+    (saved, scratch) for n == 2."""
+    outs = [ctypes.c_size_t() for _ in range(n)]
+    _check(getattr(_lib or load_library(), name)(*args, *outs), name)
+    return outs[0].value if n == 1 else tuple(o.value for o in outs)
+
+
+def _buf(t: torch.Tensor):
+    """A uint8 workspace as the (pointer, byte count) pair of arguments the C ABI takes."""
+    return t, t.numel()
+
+
+def _ptr_array(ts):
+    """The host array of device pointers of ``ts`` (a None entry is NULL)."""
+    return (ctypes.c_void_p * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
+
+
+def _workspace(ws, need: int, dev, what: str = "workspace", too_small: str = "replace"):
+    """A uint8 buffer for a call that needs ``need`` bytes: a fresh one of max(need, 16) bytes without ``ws``, else
+    ``ws`` once its dtype, device and contiguity are checked.  A supplied buffer below ``need`` is, by
+    ``too_small``: "replace" -- silently replaced by a fresh one; "raise" -- a ValueError naming the byte count;
+    "pass" -- handed on as it is (the C ABI answers HN_ERR_WORKSPACE)."""
+    if ws is not None:
+        if ws.dtype != torch.uint8 or ws.device != dev or not ws.is_contiguous():
+            raise ValueError(f"{what} must be a contiguous uint8 tensor on {dev}")
+        if ws.numel() >= need or too_small == "pass":
+            return ws
+        if too_small == "raise":
+            raise ValueError(f"{what} must be a contiguous uint8 tensor of at least {need} bytes on {dev}")
+    return torch.empty(max(need, 16), device=dev, dtype=torch.uint8)
+
+
+def _out(t, shape, dev, what: str = "out", dtype=torch.float32):
+    """The destination of an output: a fresh tensor without ``t``, else ``t`` once its shape, dtype, device and
+    contiguity are checked."""
+    if t is None:
+        return torch.empty(shape, device=dev, dtype=dtype)
+    if tuple(t.shape) != tuple(shape) or t.dtype != dtype or t.device != dev or not t.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous {dtype} {list(shape)} tensor on {dev}, got {t.dtype} "
+                         f"{tuple(t.shape)} on {t.device}")
+    return t
+
+
+def _aligned16(x: torch.Tensor) -> torch.Tensor:
+    """A contiguous, detached x whose rows the C ABI can take (16-byte aligned: a contiguous view at an odd
+    storage offset is copied)."""
+    x = x.detach().contiguous()
+    return x if x.data_ptr() % 16 == 0 else x.clone()
+
+
+def _grad_slots(tensors):
+    """Per tensor of a train ABI's table: 1 = a parameter whose gradient is returned, 2 = a frozen parameter (the
+    kernels still write its gradient: it gets a throwaway buffer), 0 = a buffer (running statistics)."""
+    return [1 if t.requires_grad else 2 if isinstance(t, torch.nn.Parameter) else 0 for t in tensors]
+
+
+def _grad_buffers(params, slots, tensors):
+    """(grads, bufs) of a train backward: ``grads`` are the gradients of ``params`` (the slot-1 tensors in order),
+    one allocation handed out as contiguous views of the parameters' shapes (the supernet has ~2,000; autograd
+    stores them as .grad without a copy); ``bufs`` is parallel to ``tensors``: those views, a throwaway buffer per
+    frozen parameter and None per running statistic."""
+    flat = torch.empty(sum(p.numel() for p in params), device=tensors[0].device, dtype=torch.float32)
+    grads = [g.view(p.shape) for g, p in zip(flat.split([p.numel() for p in params]), params)]
+    it = iter(grads)
+    return grads, [next(it) if k == 1 else torch.empty_like(t) if k == 2 else None for k, t in zip(slots, tensors)]
+
+
 # ----------------------------------------------------------------------------------
 # descriptors and parameter blobs
 # ----------------------------------------------------------------------------------
 def hardnet_desc(input_norm_eps: float = 1e-7, l2_eps: float = 1e-10) -> HnArchDesc:
-    d = HnArchDesc()
-    d.kind = HN_KIND_HARDNET
-    d.input_norm_eps = input_norm_eps
-    d.l2_eps = l2_eps
-    d.bn_eps = 1e-5
-    return d
+    return HnArchDesc(kind=HN_KIND_HARDNET, input_norm_eps=input_norm_eps, l2_eps=l2_eps, bn_eps=1e-5)
 
 
 def nas_desc(ops: List[str], layers=None, input_norm_eps: float = -1.0,
              l2_eps: float = 0.0) -> HnArchDesc:
     layers = layers or A.SEARCH_SPACE2
-    d = HnArchDesc()
-    d.kind = HN_KIND_NAS
-    d.n_layers = len(ops)
+    d = HnArchDesc(kind=HN_KIND_NAS, n_layers=len(ops), input_norm_eps=input_norm_eps, l2_eps=l2_eps, bn_eps=1e-5)
     for i, (op, (ci, co, s)) in enumerate(zip(ops, layers)):
         d.op[i] = A.CANDIDATE_BLOCKS.index(op)
         d.c_in[i], d.c_out[i], d.stride[i] = ci, co, s
-    d.input_norm_eps = input_norm_eps
-    d.l2_eps = l2_eps
-    d.bn_eps = 1e-5
     return d
 
 
@@ -248,14 +313,12 @@ class NativeModel:
         self.lib = load_library()
         self.device = torch.device(device)
         self.desc = desc
-        n = ctypes.c_size_t()
-        _check(self.lib.hn_param_count(ctypes.byref(desc), ctypes.byref(n)), "hn_param_count")
-        if n.value != blob.size:
-            raise ValueError(f"parameter blob has {blob.size} floats, library expects {n.value}")
+        n = _size("hn_param_count", desc)
+        if n != blob.size:
+            raise ValueError(f"parameter blob has {blob.size} floats, library expects {n}")
         h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
-            _check(self.lib.hn_create(ctypes.byref(desc), blob.ctypes.data, blob.size,
-                                      ctypes.byref(h)), "hn_create")
+            _check(self.lib.hn_create(desc, blob.ctypes.data, blob.size, h), "hn_create")
         self._h = h
 
     @classmethod
@@ -263,9 +326,13 @@ class NativeModel:
         return cls(desc_for_module(module), state_dict_blob(module.state_dict()), device)
 
     def workspace_bytes(self, batch: int) -> int:
-        n = ctypes.c_size_t()
-        _check(self.lib.hn_workspace_bytes(self._h, batch, ctypes.byref(n)), "hn_workspace_bytes")
-        return n.value
+        return _size("hn_workspace_bytes", self._h, batch)
+
+    def workspace_bytes_u8(self, batch: int) -> int:
+        return _size("hn_workspace_bytes_u8", self._h, batch)
+
+    def workspace_bytes_kp(self, n: int) -> int:
+        return _size("hn_workspace_bytes_kp", self._h, n)
 
     def forward(self, x: torch.Tensor, out: Optional[torch.Tensor] = None,
                 workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -275,23 +342,9 @@ class NativeModel:
             raise ValueError(f"expected fp32 [B,1,32,32], got {x.dtype} {tuple(x.shape)}")
         x = x.contiguous()
         b = x.shape[0]
-        if out is None:
-            out = torch.empty((b, 128), device=self.device, dtype=torch.float32)
-        elif (tuple(out.shape) != (b, 128) or out.dtype != torch.float32 or out.device != self.device
-              or not out.is_contiguous()):
-            raise ValueError(f"out must be a contiguous fp32 [{b},128] tensor on {self.device}, got "
-                             f"{out.dtype} {tuple(out.shape)} on {out.device}")
-        ws_bytes = self.workspace_bytes(b)
-        if workspace is not None and (workspace.dtype != torch.uint8 or workspace.device != self.device
-                                      or not workspace.is_contiguous()):
-            raise ValueError(f"workspace must be a contiguous uint8 tensor on {self.device}")
-        if workspace is None or workspace.numel() < ws_bytes:
-            workspace = torch.empty(max(ws_bytes, 16), device=self.device, dtype=torch.uint8)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        with torch.cuda.device(self.device):
-            _check(self.lib.hn_forward(self._h, x.data_ptr(), b, out.data_ptr(),
-                                       workspace.data_ptr(), workspace.numel(), stream),
-                   "hn_forward")
+        out = _out(out, (b, 128), self.device)
+        workspace = _workspace(workspace, self.workspace_bytes(b), self.device)
+        _call(self.device, "hn_forward", self._h, x, b, out, *_buf(workspace))
         return out
 
     __call__ = forward
@@ -302,43 +355,12 @@ class NativeModel:
         """Descriptors straight from uint8 patches ([n,64,64] / [n,1,64,64]; [n,32,32] for
         resize='none'): the loader transforms (hardnet/HardNet.py:333-337, 345-349) fused into the
         forward -- equal to ``forward(preprocess(u8, ...))`` bit for bit."""
-        if resize not in RESIZE_MODES:
-            raise ValueError(f"resize must be one of {sorted(RESIZE_MODES)}")
-        if u8.dtype != torch.uint8 or u8.device != self.device:
-            raise ValueError(f"expected a uint8 tensor on {self.device}")
-        hw = 32 if resize == "none" else 64
-        b = u8.shape[0]
-        if u8.numel() != b * hw * hw:
-            raise ValueError(f"expected {hw}x{hw} patches, got shape {tuple(u8.shape)}")
-        x = u8.contiguous()
-        if out is None:
-            out = torch.empty((b, 128), device=self.device, dtype=torch.float32)
-        elif (tuple(out.shape) != (b, 128) or out.dtype != torch.float32 or out.device != self.device
-              or not out.is_contiguous()):
-            raise ValueError(f"out must be a contiguous fp32 [{b},128] tensor on {self.device}")
-        n = ctypes.c_size_t()
-        _check(self.lib.hn_workspace_bytes_u8(self._h, b, ctypes.byref(n)), "hn_workspace_bytes_u8")
-        if workspace is not None and (workspace.dtype != torch.uint8 or workspace.device != self.device
-                                      or not workspace.is_contiguous()):
-            raise ValueError(f"workspace must be a contiguous uint8 tensor on {self.device}")
-        if workspace is None or workspace.numel() < n.value:
-            workspace = torch.empty(max(n.value, 16), device=self.device, dtype=torch.uint8)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        with torch.cuda.device(self.device):
-            _check(self.lib.hn_forward_u8(self._h, x.data_ptr(), b, hw, RESIZE_MODES[resize], int(normalize),
-                                          mean, std, out.data_ptr(), workspace.data_ptr(), workspace.numel(),
-                                          stream), "hn_forward_u8")
+        x, b, hw = _u8_patches(u8, resize, self.device)
+        out = _out(out, (b, 128), self.device)
+        workspace = _workspace(workspace, self.workspace_bytes_u8(b), self.device)
+        _call(self.device, "hn_forward_u8", self._h, x, b, hw, RESIZE_MODES[resize], int(normalize), mean, std, out,
+              *_buf(workspace))
         return out
-
-    def workspace_bytes_u8(self, batch: int) -> int:
-        n = ctypes.c_size_t()
-        _check(self.lib.hn_workspace_bytes_u8(self._h, batch, ctypes.byref(n)), "hn_workspace_bytes_u8")
-        return n.value
-
-    def workspace_bytes_kp(self, n: int) -> int:
-        sz = ctypes.c_size_t()
-        _check(self.lib.hn_workspace_bytes_kp(self._h, n, ctypes.byref(sz)), "hn_workspace_bytes_kp")
-        return sz.value
 
     def forward_keypoints(self, images: torch.Tensor, kpts: torch.Tensor, scale: torch.Tensor,
                           ori: Optional[torch.Tensor], ratio: torch.Tensor, out: Optional[torch.Tensor] = None,
@@ -347,23 +369,10 @@ class NativeModel:
         workspace a chunk at a time and never leave it -- equal to ``forward(clip_patch(...))`` bit for bit."""
         im, kp, sc, orr, ra = _keypoint_args(images, kpts, scale, ori, ratio, self.device)
         n = kp.shape[0]
-        if out is None:
-            out = torch.empty((n, 128), device=self.device, dtype=torch.float32)
-        elif (tuple(out.shape) != (n, 128) or out.dtype != torch.float32 or out.device != self.device
-              or not out.is_contiguous()):
-            raise ValueError(f"out must be a contiguous fp32 [{n},128] tensor on {self.device}")
-        need = self.workspace_bytes_kp(n)
-        if workspace is not None and (workspace.dtype != torch.uint8 or workspace.device != self.device
-                                      or not workspace.is_contiguous()):
-            raise ValueError(f"workspace must be a contiguous uint8 tensor on {self.device}")
-        if workspace is None or workspace.numel() < need:
-            workspace = torch.empty(max(need, 16), device=self.device, dtype=torch.uint8)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        with torch.cuda.device(self.device):
-            _check(self.lib.hn_forward_kp(self._h, im.data_ptr(), im.shape[0], im.shape[2], im.shape[3],
-                                          kp.data_ptr(), sc.data_ptr(), orr.data_ptr() if orr is not None else None,
-                                          ra.data_ptr(), n, out.data_ptr(), workspace.data_ptr(), workspace.numel(),
-                                          stream), "hn_forward_kp")
+        out = _out(out, (n, 128), self.device)
+        workspace = _workspace(workspace, self.workspace_bytes_kp(n), self.device)
+        _call(self.device, "hn_forward_kp", self._h, im, im.shape[0], im.shape[2], im.shape[3], kp, sc, orr, ra, n,
+              out, *_buf(workspace))
         return out
 
     def set_profiling(self, on: bool):
@@ -396,22 +405,15 @@ class NativeModel:
 def pairdist_hardneg(anchor: torch.Tensor, positive: torch.Tensor, anchor_swap: bool = False):
     """(pos, min_neg) of loss_HardNet's 'min' batch_reduce (hardnet/Losses.py:87-110),
     computed by the fused kernel without materialising the BxB distance matrix."""
-    lib = load_library()
     if anchor.shape != positive.shape or anchor.dim() != 2:
         raise ValueError("anchor/positive must be equal [B,D]")
     a = anchor.contiguous().float()
     p = positive.contiguous().float()
     b, d = a.shape
-    n = ctypes.c_size_t()
-    _check(lib.hn_pairdist_workspace_bytes(b, ctypes.byref(n)), "hn_pairdist_workspace_bytes")
-    ws = torch.empty(max(n.value, 16), device=a.device, dtype=torch.uint8)
+    ws = _workspace(None, _size("hn_pairdist_workspace_bytes", b), a.device)
     pos = torch.empty(b, device=a.device, dtype=torch.float32)
     mn = torch.empty(b, device=a.device, dtype=torch.float32)
-    stream = torch.cuda.current_stream(a.device).cuda_stream
-    with torch.cuda.device(a.device):
-        _check(lib.hn_pairdist_hardneg(a.data_ptr(), p.data_ptr(), b, d, int(anchor_swap),
-                                       pos.data_ptr(), mn.data_ptr(), ws.data_ptr(), ws.numel(),
-                                       stream), "hn_pairdist_hardneg")
+    _call(a.device, "hn_pairdist_hardneg", a, p, b, d, int(anchor_swap), pos, mn, *_buf(ws))
     return pos, mn
 
 
@@ -419,28 +421,18 @@ def pairdist_rows(anchor_rows: torch.Tensor, row0: int, positive: torch.Tensor, 
     """Rows [row0, row0 + n) of loss_HardNet's masked distance matrix (hardnet/Losses.py:95-108)
     between this rank's anchors and all positives: (pos, row_min, col_min or None); col_min[j]
     is the masked minimum of column j over these rows only (all-reduce it with MIN)."""
-    lib = load_library()
     a = anchor_rows.contiguous().float()
     p = positive.contiguous().float()
     if a.dim() != 2 or p.dim() != 2 or a.shape[1] != p.shape[1] or a.device != p.device:
         raise ValueError("expected [n,D] anchors and [B,D] positives on one device")
     n, d = a.shape
     b = p.shape[0]
-    sz = ctypes.c_size_t()
-    _check(lib.hn_pairdist_rows_workspace_bytes(n, b, ctypes.byref(sz)), "hn_pairdist_rows_workspace_bytes")
-    ws = torch.empty(max(sz.value, 16), device=a.device, dtype=torch.uint8)
+    ws = _workspace(None, _size("hn_pairdist_rows_workspace_bytes", n, b), a.device)
     pos = torch.empty(n, device=a.device, dtype=torch.float32)
     rmin = torch.empty(n, device=a.device, dtype=torch.float32)
     cmin = torch.empty(b, device=a.device, dtype=torch.float32) if col_min else None
-    stream = torch.cuda.current_stream(a.device).cuda_stream
-    with torch.cuda.device(a.device):
-        _check(lib.hn_pairdist_rows(a.data_ptr(), n, int(row0), p.data_ptr(), b, d, pos.data_ptr(),
-                                    rmin.data_ptr(), cmin.data_ptr() if cmin is not None else None,
-                                    ws.data_ptr(), ws.numel(), stream), "hn_pairdist_rows")
+    _call(a.device, "hn_pairdist_rows", a, n, int(row0), p, b, d, pos, rmin, cmin, *_buf(ws))
     return pos, rmin, cmin
-
-
-LOSS_TYPES = {"triplet_margin": 0, "softmax": 1, "contrastive": 2}  # enum hn_loss_type
 
 
 class HardNetLossFunction(torch.autograd.Function):
@@ -451,38 +443,25 @@ class HardNetLossFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, anchor, positive, anchor_swap, margin, loss_type):
-        lib = load_library()
-        # the C ABI takes 16-byte aligned rows: a contiguous view at an odd storage offset is copied
-        a, p = (x if x.data_ptr() % 16 == 0 else x.clone() for x in
-                (anchor.detach().contiguous(), positive.detach().contiguous()))
+        a, p = _aligned16(anchor), _aligned16(positive)
         b = a.shape[0]
-        n = ctypes.c_size_t()
-        _check(lib.hn_hardnet_loss_train_workspace_bytes(b, ctypes.byref(n)), "hn_hardnet_loss_train_workspace_bytes")
-        saved = torch.empty(n.value, device=a.device, dtype=torch.uint8)
+        saved = torch.empty(_size("hn_hardnet_loss_train_workspace_bytes", b), device=a.device, dtype=torch.uint8)
         loss = torch.empty((), device=a.device, dtype=torch.float32)
-        stream = torch.cuda.current_stream(a.device).cuda_stream
-        with torch.cuda.device(a.device):
-            _check(lib.hn_hardnet_loss_train_forward(a.data_ptr(), p.data_ptr(), b, a.shape[1], int(bool(anchor_swap)),
-                                                     float(margin), LOSS_TYPES[loss_type], loss.data_ptr(),
-                                                     saved.data_ptr(), saved.numel(), stream),
-                   "hn_hardnet_loss_train_forward")
-        ctx.args = (bool(anchor_swap), float(margin), LOSS_TYPES[loss_type])
+        swap, margin, lt = ctx.args = (bool(anchor_swap), float(margin), LOSS_TYPES[loss_type])
+        _call(a.device, "hn_hardnet_loss_train_forward", a, p, b, a.shape[1], int(swap), margin, lt, loss,
+              *_buf(saved))
         ctx.save_for_backward(a, p, saved)
         return loss
 
     @staticmethod
     @torch.autograd.function.once_differentiable  # the fused backward records no graph (no double backward)
     def backward(ctx, dloss):
-        lib = load_library()
         a, p, saved = ctx.saved_tensors
         swap, margin, lt = ctx.args
         ga, gp = torch.empty_like(a), torch.empty_like(p)
         dl = dloss.detach().to(device=a.device, dtype=torch.float32).contiguous().reshape(1)
-        stream = torch.cuda.current_stream(a.device).cuda_stream
-        with torch.cuda.device(a.device):
-            _check(lib.hn_hardnet_loss_backward(a.data_ptr(), p.data_ptr(), a.shape[0], a.shape[1], int(swap), margin,
-                                                lt, dl.data_ptr(), ga.data_ptr(), gp.data_ptr(), saved.data_ptr(),
-                                                saved.numel(), stream), "hn_hardnet_loss_backward")
+        _call(a.device, "hn_hardnet_loss_backward", a, p, a.shape[0], a.shape[1], int(swap), margin, lt, dl, ga, gp,
+              *_buf(saved))
         return ga, gp, None, None, None
 
 
@@ -498,31 +477,18 @@ def hardnet_loss_saved_argmins(saved: torch.Tensor, b: int):
     return keys[:b] & 0xffffffff, keys[blk // 8:blk // 8 + b] & 0xffffffff
 
 
-def _aligned16(x: torch.Tensor) -> torch.Tensor:
-    """A contiguous, detached x whose rows the C ABI can take (16-byte aligned: a contiguous view at an odd
-    storage offset is copied)."""
-    x = x.detach().contiguous()
-    return x if x.data_ptr() % 16 == 0 else x.clone()
-
-
 def neimask_loss_forward(anchor, positive, anchor_kp, positive_kp, margin: float = 1.0, C: float = 5.0):
     """``hn_neimask_loss_forward`` on fp32 [N,128] descriptors and int64 [N,4] keypoints of one HIP device.
     Returns (loss [], pos [N], min_neg [N], saved): ``saved`` is the uint8 workspace the backward reads --
     row keys [N] u64 then column keys [N] u64 (value bits << 32 | argmin), each block 256-byte aligned
     (``neimask_saved_argmins``)."""
-    lib = load_library()
     a, p, ak, pk = (_aligned16(x) for x in (anchor, positive, anchor_kp, positive_kp))
     b = a.shape[0]
-    n = ctypes.c_size_t()
-    _check(lib.hn_neimask_loss_workspace_bytes(b, ctypes.byref(n)), "hn_neimask_loss_workspace_bytes")
-    saved = torch.empty(n.value, device=a.device, dtype=torch.uint8)
+    saved = torch.empty(_size("hn_neimask_loss_workspace_bytes", b), device=a.device, dtype=torch.uint8)
     loss = torch.empty((), device=a.device, dtype=torch.float32)
     pos, mn = (torch.empty(b, device=a.device, dtype=torch.float32) for _ in range(2))
-    stream = torch.cuda.current_stream(a.device).cuda_stream
-    with torch.cuda.device(a.device):
-        _check(lib.hn_neimask_loss_forward(a.data_ptr(), p.data_ptr(), ak.data_ptr(), pk.data_ptr(), b, a.shape[1],
-                                           float(margin), float(C), loss.data_ptr(), pos.data_ptr(), mn.data_ptr(),
-                                           saved.data_ptr(), saved.numel(), stream), "hn_neimask_loss_forward")
+    _call(a.device, "hn_neimask_loss_forward", a, p, ak, pk, b, a.shape[1], float(margin), float(C), loss, pos, mn,
+          *_buf(saved))
     return loss, pos, mn, saved
 
 
@@ -550,15 +516,10 @@ class NeiMaskLossFunction(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable  # the fused backward records no graph (no double backward)
     def backward(ctx, dloss):
-        lib = load_library()
         a, p, saved = ctx.saved_tensors
         ga, gp = torch.empty_like(a), torch.empty_like(p)
         dl = dloss.detach().to(device=a.device, dtype=torch.float32).contiguous().reshape(1)
-        stream = torch.cuda.current_stream(a.device).cuda_stream
-        with torch.cuda.device(a.device):
-            _check(lib.hn_neimask_loss_backward(a.data_ptr(), p.data_ptr(), a.shape[0], a.shape[1], ctx.margin,
-                                                dl.data_ptr(), ga.data_ptr(), gp.data_ptr(), saved.data_ptr(),
-                                                saved.numel(), stream), "hn_neimask_loss_backward")
+        _call(a.device, "hn_neimask_loss_backward", a, p, a.shape[0], a.shape[1], ctx.margin, dl, ga, gp, *_buf(saved))
         return ga, gp, None, None, None, None
 
 
@@ -566,7 +527,6 @@ def hardnet_loss(pos: torch.Tensor, row_min: torch.Tensor, col_min: Optional[tor
                  margin: float = 1.0, loss_type: str = "triplet_margin", scale: Optional[float] = None):
     """scale * sum of loss_HardNet's per-row margin loss (Losses.py:142-153; scale defaults to
     1/n = torch.mean) with min_neg = min(row_min, col_min): (loss [1], min_neg [n])."""
-    lib = load_library()
     if loss_type not in LOSS_TYPES:
         raise ValueError(f"loss_type must be one of {sorted(LOSS_TYPES)}")
     n = pos.shape[0]
@@ -574,44 +534,29 @@ def hardnet_loss(pos: torch.Tensor, row_min: torch.Tensor, col_min: Optional[tor
     cm = col_min.contiguous().float() if col_min is not None else None
     mn = torch.empty(n, device=ps.device, dtype=torch.float32)
     loss = torch.empty(1, device=ps.device, dtype=torch.float32)
-    stream = torch.cuda.current_stream(ps.device).cuda_stream
-    with torch.cuda.device(ps.device):
-        _check(lib.hn_hardnet_loss(ps.data_ptr(), rm.data_ptr(), cm.data_ptr() if cm is not None else None,
-                                   n, float(margin), LOSS_TYPES[loss_type],
-                                   float(1.0 / n if scale is None else scale), mn.data_ptr(),
-                                   loss.data_ptr(), stream), "hn_hardnet_loss")
+    _call(ps.device, "hn_hardnet_loss", ps, rm, cm, n, float(margin), LOSS_TYPES[loss_type],
+          float(1.0 / n if scale is None else scale), mn, loss)
     return loss, mn
 
 
 def fpr95(out_a: torch.Tensor, out_p: torch.Tensor, labels: torch.Tensor):
     """(fpr95, pair distances) on device: the eval loop of hardnet/HardNet.py:450-472
     (``sqrt(sum((a-p)^2))`` per pair) + ``ErrorRateAt95Recall`` (EvalMetrics.py:6-19)."""
-    lib = load_library()
     if out_a.shape != out_p.shape or out_a.dim() != 2 or labels.numel() != out_a.shape[0]:
         raise ValueError("expected [n,D] descriptors and [n] labels")
     a = out_a.contiguous().float()
     p = out_p.contiguous().float()
     lab = labels.to(device=a.device, dtype=torch.int32).contiguous()
     n, d = a.shape
-    sz = ctypes.c_size_t()
-    _check(lib.hn_fpr95_workspace_bytes(n, ctypes.byref(sz)), "hn_fpr95_workspace_bytes")
-    ws = torch.empty(max(sz.value, 16), device=a.device, dtype=torch.uint8)
+    ws = _workspace(None, _size("hn_fpr95_workspace_bytes", n), a.device)
     dists = torch.empty(n, device=a.device, dtype=torch.float32)
     res = torch.empty(1, device=a.device, dtype=torch.float64)
-    stream = torch.cuda.current_stream(a.device).cuda_stream
-    with torch.cuda.device(a.device):
-        _check(lib.hn_fpr95(a.data_ptr(), p.data_ptr(), lab.data_ptr(), n, d, dists.data_ptr(),
-                            res.data_ptr(), ws.data_ptr(), ws.numel(), stream), "hn_fpr95")
+    _call(a.device, "hn_fpr95", a, p, lab, n, d, dists, res, *_buf(ws))
     return float(res.item()), dists
 
 
-MATCH_METRICS = {"unit": 0, "l2": 1}  # enum hn_metric
-
-
 def match_workspace_bytes(n_query: int, n_db: int) -> int:
-    n = ctypes.c_size_t()
-    _check(load_library().hn_match_workspace_bytes(n_query, n_db, ctypes.byref(n)), "hn_match_workspace_bytes")
-    return n.value
+    return _size("hn_match_workspace_bytes", n_query, n_db)
 
 
 def match_nn2(query: torch.Tensor, db: torch.Tensor, metric: str = "unit",
@@ -622,29 +567,19 @@ def match_nn2(query: torch.Tensor, db: torch.Tensor, metric: str = "unit",
     (math_utils.py:8-19, unit descriptors), 'l2' HardNet's (hardnet/Losses.py:5-13).  Equal keys are
     ordered by database index (include/hardnet_mi355x.h).  The workspace comes from torch's caching
     allocator unless one of at least match_workspace_bytes(N, M) bytes is passed."""
-    lib = load_library()
     if metric not in MATCH_METRICS:
         raise ValueError(f"metric must be one of {sorted(MATCH_METRICS)}")
     if query.dim() != 2 or db.dim() != 2 or query.shape[1] != db.shape[1] or query.device != db.device:
         raise ValueError("expected [N,D] queries and [M,D] database rows on one device")
     if not query.is_cuda or query.dtype != torch.float32 or db.dtype != torch.float32:
         raise ValueError("expected fp32 HIP tensors")
-    # the C ABI takes 16-byte aligned rows: a contiguous view at an odd storage offset is copied
-    q, b = (x if x.data_ptr() % 16 == 0 else x.clone() for x in (query.contiguous(), db.contiguous()))
+    q, b = _aligned16(query), _aligned16(db)
     n, d = q.shape
     m = b.shape[0]
-    need = match_workspace_bytes(n, m)
-    if workspace is not None and (workspace.dtype != torch.uint8 or workspace.device != q.device
-                                  or not workspace.is_contiguous()):
-        raise ValueError(f"workspace must be a contiguous uint8 tensor on {q.device}")
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(max(need, 16), device=q.device, dtype=torch.uint8)
+    workspace = _workspace(workspace, match_workspace_bytes(n, m), q.device)
     dist = torch.empty((n, 2), device=q.device, dtype=torch.float32)
     idx = torch.empty((n, 2), device=q.device, dtype=torch.int32)
-    stream = torch.cuda.current_stream(q.device).cuda_stream
-    with torch.cuda.device(q.device):
-        _check(lib.hn_match_nn2(q.data_ptr(), n, b.data_ptr(), m, d, MATCH_METRICS[metric], dist.data_ptr(),
-                                idx.data_ptr(), workspace.data_ptr(), workspace.numel(), stream), "hn_match_nn2")
+    _call(q.device, "hn_match_nn2", q, n, b, m, d, MATCH_METRICS[metric], dist, idx, *_buf(workspace))
     return dist, idx
 
 
@@ -681,19 +616,10 @@ def clip_patch(images: torch.Tensor, kpts: torch.Tensor, scale: torch.Tensor, or
     or None, ratio fp32 [B] (im_info[:,0]), all on one HIP device -> fp32 [N,1,32,32].  Column 0 of a keypoint
     selects its image and its ratio; the call reads nothing outside ``images`` whatever the keypoint data
     (include/hardnet_mi355x.h)."""
-    lib = load_library()
     im, kp, sc, orr, ra = _keypoint_args(images, kpts, scale, ori, ratio)
     n = kp.shape[0]
-    if out is None:
-        out = torch.empty((n, 1, 32, 32), device=im.device, dtype=torch.float32)
-    elif (tuple(out.shape) != (n, 1, 32, 32) or out.dtype != torch.float32 or out.device != im.device
-          or not out.is_contiguous()):
-        raise ValueError(f"out must be a contiguous fp32 [{n},1,32,32] tensor on {im.device}")
-    stream = torch.cuda.current_stream(im.device).cuda_stream
-    with torch.cuda.device(im.device):
-        _check(lib.hn_clip_patch(im.data_ptr(), im.shape[0], im.shape[2], im.shape[3], kp.data_ptr(), sc.data_ptr(),
-                                 orr.data_ptr() if orr is not None else None, ra.data_ptr(), n, out.data_ptr(),
-                                 stream), "hn_clip_patch")
+    out = _out(out, (n, 1, 32, 32), im.device)
+    _call(im.device, "hn_clip_patch", im, im.shape[0], im.shape[2], im.shape[3], kp, sc, orr, ra, n, out)
     return out
 
 
@@ -707,7 +633,6 @@ def clip_patch_backward(dout: torch.Tensor, images: torch.Tensor, kpts: torch.Te
     ``want_ori`` without ``ori`` is an error.  ``out_scale`` / ``out_ori`` are optional contiguous destinations.
     A keypoint's gradient is bit-identical call to call, alone or in any batch; the call reads nothing outside
     ``images`` whatever the keypoint data (include/hardnet_mi355x.h)."""
-    lib = load_library()
     im, kp, sc, orr, ra = _keypoint_args(images, kpts, scale, ori, ratio)
     n = kp.shape[0]
     if want_ori and orr is None:
@@ -716,23 +641,10 @@ def clip_patch_backward(dout: torch.Tensor, images: torch.Tensor, kpts: torch.Te
         raise ValueError(f"dout must be fp32 [{n},1,32,32] on {im.device}, got {dout.dtype} {tuple(dout.shape)} "
                          f"on {dout.device}")
     dout = dout.contiguous()
-
-    def dest(t, shape, what):
-        if t is None:
-            return torch.empty(shape, device=im.device, dtype=torch.float32)
-        if tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != im.device or not t.is_contiguous():
-            raise ValueError(f"{what} must be a contiguous fp32 {list(shape)} tensor on {im.device}")
-        return t
-
-    ds = dest(out_scale, (n,), "out_scale") if want_scale else None
-    do = dest(out_ori, (n, 2), "out_ori") if want_ori else None
-    stream = torch.cuda.current_stream(im.device).cuda_stream
-    with torch.cuda.device(im.device):
-        _check(lib.hn_clip_patch_backward(dout.data_ptr(), im.data_ptr(), im.shape[0], im.shape[2], im.shape[3],
-                                          kp.data_ptr(), sc.data_ptr(), orr.data_ptr() if orr is not None else None,
-                                          ra.data_ptr(), n, ds.data_ptr() if ds is not None else None,
-                                          do.data_ptr() if do is not None else None, stream),
-               "hn_clip_patch_backward")
+    ds = _out(out_scale, (n,), im.device, "out_scale") if want_scale else None
+    do = _out(out_ori, (n, 2), im.device, "out_ori") if want_ori else None
+    _call(im.device, "hn_clip_patch_backward", dout, im, im.shape[0], im.shape[2], im.shape[3], kp, sc, orr, ra, n,
+          ds, do)
     return ds, do
 
 
@@ -770,21 +682,17 @@ class NativeDetector:
     def __init__(self, blob: np.ndarray, device, bn_eps: float = 1e-5, in_eps: float = 1e-5):
         self.lib = load_library()
         self.device = torch.device(device)
-        n = ctypes.c_size_t()
-        _check(self.lib.hn_det_param_count(ctypes.byref(n)), "hn_det_param_count")
-        if n.value != blob.size:
-            raise ValueError(f"parameter blob has {blob.size} floats, library expects {n.value}")
+        n = _size("hn_det_param_count")
+        if n != blob.size:
+            raise ValueError(f"parameter blob has {blob.size} floats, library expects {n}")
         h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
-            _check(self.lib.hn_det_create(blob.ctypes.data, blob.size, bn_eps, in_eps, ctypes.byref(h)),
-                   "hn_det_create")
+            _check(self.lib.hn_det_create(blob.ctypes.data, blob.size, bn_eps, in_eps, h), "hn_det_create")
         self._h = h
         self._ws = None  # workspace cache: grows, never shrinks
 
     def workspace_bytes(self, n_images: int, height: int, width: int) -> int:
-        n = ctypes.c_size_t()
-        _check(self.lib.hn_det_workspace_bytes(n_images, height, width, ctypes.byref(n)), "hn_det_workspace_bytes")
-        return n.value
+        return _size("hn_det_workspace_bytes", n_images, height, width)
 
     def forward(self, images: torch.Tensor, score: Optional[torch.Tensor] = None, ori: Optional[torch.Tensor] = None,
                 workspace: Optional[torch.Tensor] = None):
@@ -795,24 +703,14 @@ class NativeDetector:
                              f"on {images.device}")
         x = images.contiguous()
         b, _, h, w = x.shape
-        if score is None:
-            score = torch.empty((b, h, w), device=self.device, dtype=torch.float32)
-        if ori is None:
-            ori = torch.empty((b, h, w, 2), device=self.device, dtype=torch.float32)
-        for t, shp in ((score, (b, h, w)), (ori, (b, h, w, 2))):
-            if tuple(t.shape) != shp or t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous():
-                raise ValueError(f"outputs must be contiguous fp32 {shp} tensors on {self.device}")
+        score = _out(score, (b, h, w), self.device, "score")
+        ori = _out(ori, (b, h, w, 2), self.device, "ori")
         need = self.workspace_bytes(b, h, w)
-        if workspace is None:
-            if self._ws is None or self._ws.numel() < need:
-                self._ws = torch.empty(max(need, 16), device=self.device, dtype=torch.uint8)
-            workspace = self._ws
-        elif workspace.dtype != torch.uint8 or workspace.device != self.device or not workspace.is_contiguous():
-            raise ValueError(f"workspace must be a contiguous uint8 tensor on {self.device}")
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        with torch.cuda.device(self.device):
-            _check(self.lib.hn_det_forward(self._h, x.data_ptr(), b, h, w, score.data_ptr(), ori.data_ptr(),
-                                           workspace.data_ptr(), workspace.numel(), stream), "hn_det_forward")
+        if workspace is None:  # the grow-only cache: replaced when it is too small for this call
+            workspace = self._ws = _workspace(self._ws, need, self.device)
+        else:  # a short one is the C ABI's HN_ERR_WORKSPACE
+            workspace = _workspace(workspace, need, self.device, too_small="pass")
+        _call(self.device, "hn_det_forward", self._h, x, b, h, w, score, ori, *_buf(workspace))
         return score, ori
 
     __call__ = forward
@@ -832,15 +730,9 @@ class NativeDetector:
 # ----------------------------------------------------------------------------------
 # the detector in train() (hn_det_train_*)
 # ----------------------------------------------------------------------------------
-DET_TRAIN_TENSORS = 40  # HN_DET_TRAIN_TENSORS
-
-
 def det_train_workspace_bytes(n_images: int, height: int, width: int):
     """(saved, scratch) bytes of hn_det_train_forward / _backward."""
-    sv, sc = ctypes.c_size_t(), ctypes.c_size_t()
-    _check(load_library().hn_det_train_workspace_bytes(n_images, height, width, ctypes.byref(sv), ctypes.byref(sc)),
-           "hn_det_train_workspace_bytes")
-    return sv.value, sc.value
+    return _size("hn_det_train_workspace_bytes", n_images, height, width, n=2)
 
 
 def det_train_tensors(det):
@@ -860,64 +752,40 @@ def _det_train_check(images, tensors):
             raise ValueError(f"tensor {i} must be contiguous fp32 on {images.device}")
 
 
-def _det_ws(t, need, dev, what):
-    if t is None:
-        return torch.empty(max(need, 16), device=dev, dtype=torch.uint8)
-    if t.dtype != torch.uint8 or t.device != dev or not t.is_contiguous() or t.numel() < need:
-        raise ValueError(f"{what} must be a contiguous uint8 tensor of at least {need} bytes on {dev}")
-    return t
-
-
 def det_train_forward(images, tensors, bn_eps: float, in_eps: float, momentum: float, score=None, ori=None,
                       saved=None, scratch=None):
     """``hn_det_train_forward``: images fp32 [B,1,H,W] -> (score [B,H,W], ori [B,H,W,2], saved).  ``tensors`` are the
     module's 40 float state tensors (det_train_tensors); the running statistics among them are updated in place.
     ``saved`` is what det_train_backward reads; outputs and workspaces may be passed in."""
-    lib = load_library()
     _det_train_check(images, tensors)
     dev = images.device
     b, _, h, w = images.shape
     n_sv, n_sc = det_train_workspace_bytes(b, h, w)
-    score = torch.empty((b, h, w), device=dev, dtype=torch.float32) if score is None else score
-    ori = torch.empty((b, h, w, 2), device=dev, dtype=torch.float32) if ori is None else ori
-    for t, shp in ((score, (b, h, w)), (ori, (b, h, w, 2))):
-        if tuple(t.shape) != shp or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous():
-            raise ValueError(f"outputs must be contiguous fp32 {shp} tensors on {dev}")
-    saved = _det_ws(saved, n_sv, dev, "saved")
-    scratch = _det_ws(scratch, n_sc, dev, "scratch")
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    with torch.cuda.device(dev):
-        _check(lib.hn_det_train_forward(images.data_ptr(), b, h, w, _ptr_array(tensors), float(bn_eps), float(in_eps),
-                                        float(momentum), score.data_ptr(), ori.data_ptr(), saved.data_ptr(),
-                                        saved.numel(), scratch.data_ptr(), scratch.numel(), stream),
-               "hn_det_train_forward")
+    score = _out(score, (b, h, w), dev, "score")
+    ori = _out(ori, (b, h, w, 2), dev, "ori")
+    saved = _workspace(saved, n_sv, dev, "saved", too_small="raise")
+    scratch = _workspace(scratch, n_sc, dev, "scratch", too_small="raise")
+    _call(dev, "hn_det_train_forward", images, b, h, w, _ptr_array(tensors), float(bn_eps), float(in_eps),
+          float(momentum), score, ori, *_buf(saved), *_buf(scratch))
     return score, ori, saved
 
 
 def det_train_backward(dscore, dori, images, tensors, grads, saved, scratch=None):
     """``hn_det_train_backward``: the upstream gradients (either may be None: zero) -> ``grads``, a list parallel to
     ``tensors`` with a buffer for every parameter and None for the running statistics."""
-    lib = load_library()
     _det_train_check(images, tensors)
     dev = images.device
     b, _, h, w = images.shape
-    _, n_sc = det_train_workspace_bytes(b, h, w)
-    scratch = _det_ws(scratch, n_sc, dev, "scratch")
-    for t, shp in ((dscore, (b, h, w)), (dori, (b, h, w, 2))):
-        if t is not None and (tuple(t.shape) != shp or t.dtype != torch.float32 or t.device != dev
-                              or not t.is_contiguous()):
-            raise ValueError(f"upstream gradients must be contiguous fp32 {shp} tensors on {dev}")
+    scratch = _workspace(scratch, det_train_workspace_bytes(b, h, w)[1], dev, "scratch", too_small="raise")
+    for t, shp, what in ((dscore, (b, h, w), "dscore"), (dori, (b, h, w, 2), "dori")):
+        if t is not None:
+            _out(t, shp, dev, what)
     for t, g in zip(tensors, grads):
         if g is not None and (g.shape != t.shape or g.dtype != torch.float32 or g.device != dev
                               or not g.is_contiguous()):
             raise ValueError("every gradient buffer must be a contiguous fp32 tensor of its parameter's shape")
-    gp = (ctypes.c_void_p * len(grads))(*[g.data_ptr() if g is not None else None for g in grads])
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    with torch.cuda.device(dev):
-        _check(lib.hn_det_train_backward(dscore.data_ptr() if dscore is not None else None,
-                                         dori.data_ptr() if dori is not None else None, images.data_ptr(), b, h, w,
-                                         _ptr_array(tensors), gp, saved.data_ptr(), saved.numel(),
-                                         scratch.data_ptr(), scratch.numel(), stream), "hn_det_train_backward")
+    _call(dev, "hn_det_train_backward", dscore, dori, images, b, h, w, _ptr_array(tensors), _ptr_array(grads),
+          *_buf(saved), *_buf(scratch))
     return grads
 
 
@@ -934,10 +802,7 @@ class DetTrainFunction(torch.autograd.Function):
         images = _aligned16(images)  # a batch cut out of a larger one may start at any float
         score, ori, saved = det_train_forward(images, tensors, bn_eps, in_eps, momentum)
         torch._foreach_add_([m.num_batches_tracked for m in bn], 1)
-        ctx.tensors = tensors
-        # per slot: 1 = a parameter whose gradient is returned, 2 = a frozen parameter (the kernels still write
-        # its gradient: it gets a throwaway buffer), 0 = a buffer (running statistics)
-        ctx.slot = [1 if t.requires_grad else 2 if isinstance(t, torch.nn.Parameter) else 0 for t in tensors]
+        ctx.tensors, ctx.slot = tensors, _grad_slots(tensors)
         ctx.set_materialize_grads(False)  # an unused output's gradient stays None: the kernels' NULL path
         ctx.save_for_backward(saved, images, *params)
         return score.unsqueeze(-1), ori
@@ -946,21 +811,14 @@ class DetTrainFunction(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, dscore, dori):
         saved, images, *params = ctx.saved_tensors
-        # one allocation for every parameter's gradient, handed out as views of the parameters' shapes
-        flat = torch.empty(sum(p.numel() for p in params), device=images.device, dtype=torch.float32)
-        grads = [g.view(p.shape) for g, p in zip(flat.split([p.numel() for p in params]), params)]
-        it = iter(grads)
-        bufs = [next(it) if k == 1 else torch.empty_like(t) if k == 2 else None for k, t in zip(ctx.slot, ctx.tensors)]
+        grads, bufs = _grad_buffers(params, ctx.slot, ctx.tensors)
         det_train_backward(_aligned16(dscore).squeeze(-1) if dscore is not None else None,
                            _aligned16(dori) if dori is not None else None, images, ctx.tensors, bufs, saved)
         return (None, None, None, None, None, None, *grads)
 
 
 def select_workspace_bytes(n_images: int, height: int, width: int, topk: int) -> int:
-    n = ctypes.c_size_t()
-    _check(load_library().hn_select_workspace_bytes(n_images, height, width, topk, ctypes.byref(n)),
-           "hn_select_workspace_bytes")
-    return n.value
+    return _size("hn_select_workspace_bytes", n_images, height, width, topk)
 
 
 def select_keypoints(score: torch.Tensor, border: int, nms_thresh: float, nms_ksize: int, topk: int,
@@ -972,23 +830,14 @@ def select_keypoints(score: torch.Tensor, border: int, nms_thresh: float, nms_ks
     order per image, ``kscore`` (the raw score), ``kscale`` (from ``scale_map`` [B,H,W] or ``scale_value``),
     ``kori`` [B K,2] from ``ori_map`` [B,H,W,2] (or None), and with ``dense`` also ``score_proc`` [B,H,W] and
     ``topk_mask`` [B,H,W] uint8.  Ties at both top-K steps go to the lowest flat index; NaN counts as 0."""
-    lib = load_library()
     if not score.is_cuda or score.dtype != torch.float32 or score.dim() != 3:
         raise ValueError(f"score must be a fp32 HIP tensor [B,H,W], got {score.dtype} {tuple(score.shape)}")
     dev = score.device
     s = score.contiguous()
     b, h, w = s.shape
-    for name, t, shp in (("scale_map", scale_map, (b, h, w)), ("ori_map", ori_map, (b, h, w, 2))):
-        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != shp or t.device != dev):
-            raise ValueError(f"{name} must be fp32 {shp} on {dev}")
-    sm = scale_map.contiguous() if scale_map is not None else None
-    om = ori_map.contiguous() if ori_map is not None else None
-    need = select_workspace_bytes(b, h, w, topk)
-    if workspace is not None and (workspace.dtype != torch.uint8 or workspace.device != dev
-                                  or not workspace.is_contiguous()):
-        raise ValueError(f"workspace must be a contiguous uint8 tensor on {dev}")
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(max(need, 16), device=dev, dtype=torch.uint8)
+    sm = _gt_map("scale_map", scale_map, (b, h, w), dev)
+    om = _gt_map("ori_map", ori_map, (b, h, w, 2), dev)
+    workspace = _workspace(workspace, select_workspace_bytes(b, h, w, topk), dev)
     n = b * topk
     out = {"kpts": torch.empty((n, 4), device=dev, dtype=torch.int64),
            "kscore": torch.empty(n, device=dev, dtype=torch.float32),
@@ -997,24 +846,15 @@ def select_keypoints(score: torch.Tensor, border: int, nms_thresh: float, nms_ks
     if dense:
         out["score_proc"] = torch.empty((b, h, w), device=dev, dtype=torch.float32)
         out["topk_mask"] = torch.empty((b, h, w), device=dev, dtype=torch.uint8)
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    with torch.cuda.device(dev):
-        _check(lib.hn_select_keypoints(s.data_ptr(), b, h, w, border, nms_thresh, nms_ksize, topk, gauss_ksize,
-                                       gauss_sigma, ptr(sm), scale_value, ptr(om), out["kpts"].data_ptr(),
-                                       out["kscore"].data_ptr(), out["kscale"].data_ptr(), ptr(out["kori"]),
-                                       ptr(out.get("score_proc")), ptr(out.get("topk_mask")), workspace.data_ptr(),
-                                       workspace.numel(), stream), "hn_select_keypoints")
+    _call(dev, "hn_select_keypoints", s, b, h, w, border, nms_thresh, nms_ksize, topk, gauss_ksize, gauss_sigma, sm,
+          scale_value, om, out["kpts"], out["kscore"], out["kscale"], out["kori"], out.get("score_proc"),
+          out.get("topk_mask"), *_buf(workspace))
     return out
 
 
 # ----------------------------------------------------------------------------------
 # homography ground-truth stage (hn_gt.hip)
 # ----------------------------------------------------------------------------------
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
-
-
 def _gt_map(name, t, shape, dev, dtype=torch.float32):
     """``t`` as the contiguous ``dtype`` tensor of ``shape`` on ``dev`` that the C ABI reads (None stays None)."""
     if t is None:
@@ -1035,7 +875,6 @@ def warp_score(score: torch.Tensor, homo: torch.Tensor, border: int = 8, align_c
                want_warped: bool = True, want_visible: bool = True):
     """gtscore's two warps in one kernel (hn_warp_score): score fp32 [B,H,W] and homo fp32 [B,3,3] on one HIP device
     -> (warped [B,H,W], visible [B,H,W]); the source reads as 0 within ``border`` pixels of an edge."""
-    lib = load_library()
     if not score.is_cuda or score.dtype != torch.float32 or score.dim() != 3:
         raise ValueError(f"score must be a fp32 HIP tensor [B,H,W], got {score.dtype} {tuple(score.shape)}")
     dev = score.device
@@ -1044,10 +883,7 @@ def warp_score(score: torch.Tensor, homo: torch.Tensor, border: int = 8, align_c
     hm = _gt_homo("homo", homo, b, dev)
     warped = torch.empty((b, h, w), device=dev, dtype=torch.float32) if want_warped else None
     visible = torch.empty((b, h, w), device=dev, dtype=torch.float32) if want_visible else None
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    with torch.cuda.device(dev):
-        _check(lib.hn_warp_score(s.data_ptr(), hm.data_ptr(), b, h, w, int(border), int(bool(align_corners)),
-                                 _ptr(warped), _ptr(visible), stream), "hn_warp_score")
+    _call(dev, "hn_warp_score", s, hm, b, h, w, int(border), int(bool(align_corners)), warped, visible)
     return warped, visible
 
 
@@ -1055,7 +891,6 @@ def gt_scale_orin(scale_map: Optional[torch.Tensor], ori_map: torch.Tensor, homo
                   homo21: torch.Tensor, scale_value: float = 32.0):
     """Network.gt_scale_orin in one kernel (hn_gt_scale_orin): ori_map fp32 [B,H,W,2], scale_map fp32 [B,H,W] or None
     (then ``scale_value`` everywhere), homographies fp32 [B,3,3] -> (gt_scale [B,H,W], gt_ori [B,H,W,2])."""
-    lib = load_library()
     if not ori_map.is_cuda or ori_map.dtype != torch.float32 or ori_map.dim() != 4 or ori_map.shape[3] != 2:
         raise ValueError(f"ori_map must be a fp32 HIP tensor [B,H,W,2], got {ori_map.dtype} {tuple(ori_map.shape)}")
     dev = ori_map.device
@@ -1065,10 +900,7 @@ def gt_scale_orin(scale_map: Optional[torch.Tensor], ori_map: torch.Tensor, homo
     h12, h21 = _gt_homo("homo12", homo12, b, dev), _gt_homo("homo21", homo21, b, dev)
     gt_scale = torch.empty((b, h, w), device=dev, dtype=torch.float32)
     gt_ori = torch.empty((b, h, w, 2), device=dev, dtype=torch.float32)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    with torch.cuda.device(dev):
-        _check(lib.hn_gt_scale_orin(_ptr(sm), float(scale_value), om.data_ptr(), h12.data_ptr(), h21.data_ptr(), b, h,
-                                    w, gt_scale.data_ptr(), gt_ori.data_ptr(), stream), "hn_gt_scale_orin")
+    _call(dev, "hn_gt_scale_orin", sm, float(scale_value), om, h12, h21, b, h, w, gt_scale, gt_ori)
     return gt_scale, gt_ori
 
 
@@ -1077,7 +909,6 @@ def mask_keypoints(mask: torch.Tensor, topk: int, scale_map: Optional[torch.Tens
     """pair's nonzero() and masked_selects (hn_mask_keypoints): mask uint8 [B,H,W] -> (kpts [B K,4] int64 rows
     (b, y, x, 0) in raster order, kscale [B K], kori [B K,2] or None, counts [B] int32 or None).  An image with fewer
     than K set pixels gets rows (b, 0, 0, 0) for the rest; nothing is read back."""
-    lib = load_library()
     if not mask.is_cuda or mask.dtype != torch.uint8 or mask.dim() != 3:
         raise ValueError(f"mask must be a uint8 HIP tensor [B,H,W], got {mask.dtype} {tuple(mask.shape)}")
     dev = mask.device
@@ -1090,11 +921,7 @@ def mask_keypoints(mask: torch.Tensor, topk: int, scale_map: Optional[torch.Tens
     kscale = torch.empty(max(n, 0), device=dev, dtype=torch.float32)
     kori = torch.empty((max(n, 0), 2), device=dev, dtype=torch.float32) if om is not None else None
     counts = torch.empty(b, device=dev, dtype=torch.int32) if want_counts else None
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    with torch.cuda.device(dev):
-        _check(lib.hn_mask_keypoints(m.data_ptr(), b, h, w, int(topk), _ptr(sm), float(scale_value), _ptr(om),
-                                     kpts.data_ptr(), kscale.data_ptr(), _ptr(kori), _ptr(counts), stream),
-               "hn_mask_keypoints")
+    _call(dev, "hn_mask_keypoints", m, b, h, w, int(topk), sm, float(scale_value), om, kpts, kscale, kori, counts)
     return kpts, kscale, kori, counts
 
 
@@ -1102,7 +929,6 @@ def project_keypoints(kpts: torch.Tensor, homo: torch.Tensor, shape, scale_map: 
                       scale_value: float = 32.0, ori_map: Optional[torch.Tensor] = None, clamp: bool = True):
     """ptCltoCr (hn_project_keypoints): kpts int64 [N,4] rows (b, y, x, .), homo fp32 [B,3,3], ``shape`` = (B, H, W) of
     the right image's maps -> (kpts_r [N,4] rows (b, y', x', 0), scale_r [N], ori_r [N,2] or None)."""
-    lib = load_library()
     if not kpts.is_cuda or kpts.dtype != torch.int64 or kpts.dim() != 2 or kpts.shape[1] != 4:
         raise ValueError(f"kpts must be an int64 HIP tensor [N,4], got {kpts.dtype} {tuple(kpts.shape)}")
     dev = kpts.device
@@ -1115,15 +941,22 @@ def project_keypoints(kpts: torch.Tensor, homo: torch.Tensor, shape, scale_map: 
     kpts_r = torch.empty((n, 4), device=dev, dtype=torch.int64)
     scale_r = torch.empty(n, device=dev, dtype=torch.float32)
     ori_r = torch.empty((n, 2), device=dev, dtype=torch.float32) if om is not None else None
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    with torch.cuda.device(dev):
-        _check(lib.hn_project_keypoints(kp.data_ptr(), n, hm.data_ptr(), b, h, w, _ptr(sm), float(scale_value),
-                                        _ptr(om), int(bool(clamp)), kpts_r.data_ptr(), scale_r.data_ptr(),
-                                        _ptr(ori_r), stream), "hn_project_keypoints")
+    _call(dev, "hn_project_keypoints", kp, n, hm, b, h, w, sm, float(scale_value), om, int(bool(clamp)), kpts_r,
+          scale_r, ori_r)
     return kpts_r, scale_r, ori_r
 
 
-RESIZE_MODES = {"none": 0, "cv2": 1, "pil": 2}  # enum hn_resize
+def _u8_patches(u8, resize, dev=None):
+    """The validated, contiguous uint8 patches of hn_preprocess / hn_forward_u8 with their count and their side."""
+    if resize not in RESIZE_MODES:
+        raise ValueError(f"resize must be one of {sorted(RESIZE_MODES)}")
+    if u8.dtype != torch.uint8 or not u8.is_cuda or dev not in (None, u8.device):
+        raise ValueError("expected a uint8 HIP tensor" + (f" on {dev}" if dev is not None else ""))
+    hw = 32 if resize == "none" else 64
+    n = u8.shape[0]
+    if u8.numel() != n * hw * hw:
+        raise ValueError(f"expected {hw}x{hw} patches, got shape {tuple(u8.shape)}")
+    return u8.contiguous(), n, hw
 
 
 def preprocess(u8: torch.Tensor, resize: str = "cv2", normalize: bool = True,
@@ -1134,24 +967,9 @@ def preprocess(u8: torch.Tensor, resize: str = "cv2", normalize: bool = True,
     resize='cv2' + normalize = ``transform`` (hardnet/HardNet.py:345-349, cv2_scale Utils.py:10-11);
     resize='pil', normalize=False = augmented ``transform_test`` (HardNet.py:333-337).
     Defaults for mean/std are the reference's --mean-image/--std-image (HardNet.py:86-89)."""
-    lib = load_library()
-    if resize not in RESIZE_MODES:
-        raise ValueError(f"resize must be one of {sorted(RESIZE_MODES)}")
-    if u8.dtype != torch.uint8 or not u8.is_cuda:
-        raise ValueError("expected a uint8 HIP tensor")
-    hw = 32 if resize == "none" else 64
-    n = u8.shape[0]
-    if u8.numel() != n * hw * hw:
-        raise ValueError(f"expected {hw}x{hw} patches, got shape {tuple(u8.shape)}")
-    x = u8.contiguous()
-    if out is None:
-        out = torch.empty((n, 1, 32, 32), device=x.device, dtype=torch.float32)
-    elif out.shape != (n, 1, 32, 32) or out.dtype != torch.float32 or not out.is_contiguous():
-        raise ValueError("out must be a contiguous fp32 [n,1,32,32] tensor")
-    stream = torch.cuda.current_stream(x.device).cuda_stream
-    with torch.cuda.device(x.device):
-        _check(lib.hn_preprocess(x.data_ptr(), n, hw, RESIZE_MODES[resize], int(normalize),
-                                 mean, std, out.data_ptr(), stream), "hn_preprocess")
+    x, n, hw = _u8_patches(u8, resize)
+    out = _out(out, (n, 1, 32, 32), x.device)
+    _call(x.device, "hn_preprocess", x, n, hw, RESIZE_MODES[resize], int(normalize), mean, std, out)
     return out
 
 
@@ -1184,17 +1002,9 @@ HARDNET_CONV_IDX = (0, 3, 6, 9, 12, 15, 19)   # features.{i}.weight (HardNet.py:
 HARDNET_BN_IDX = (1, 4, 7, 10, 13, 16, 20)
 
 
-def _ptr_array(ts):
-    return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-
-
 def train_workspace_bytes(batch: int):
     """(saved, scratch) bytes of hn_hardnet_train_forward / _backward for a batch."""
-    lib = load_library()
-    sv, sc = ctypes.c_size_t(), ctypes.c_size_t()
-    _check(lib.hn_hardnet_train_workspace_bytes(batch, ctypes.byref(sv), ctypes.byref(sc)),
-           "hn_hardnet_train_workspace_bytes")
-    return sv.value, sc.value
+    return _size("hn_hardnet_train_workspace_bytes", batch, n=2)
 
 
 class HardNetTrainFunction(torch.autograd.Function):
@@ -1212,21 +1022,15 @@ class HardNetTrainFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, drop_p, seed, bn, *weights):
-        lib = load_library()
         b = x.shape[0]
         n_sv, n_sc = train_workspace_bytes(b)
         saved = torch.empty(n_sv, device=x.device, dtype=torch.uint8)
         scratch = torch.empty(n_sc, device=x.device, dtype=torch.uint8)
         out = torch.empty((b, 128), device=x.device, dtype=torch.float32)
         ws_w = [w.detach().contiguous() for w in weights]
-        rm = [m.running_mean for m in bn]
-        rv = [m.running_var for m in bn]
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        with torch.cuda.device(x.device):
-            _check(lib.hn_hardnet_train_forward(x.data_ptr(), b, _ptr_array(ws_w), _ptr_array(rm), _ptr_array(rv),
-                                                float(bn[0].momentum), float(drop_p), int(seed), out.data_ptr(),
-                                                saved.data_ptr(), saved.numel(), scratch.data_ptr(), scratch.numel(),
-                                                stream), "hn_hardnet_train_forward")
+        _call(x.device, "hn_hardnet_train_forward", x, b, _ptr_array(ws_w), _ptr_array([m.running_mean for m in bn]),
+              _ptr_array([m.running_var for m in bn]), float(bn[0].momentum), float(drop_p), int(seed), out,
+              *_buf(saved), *_buf(scratch))
         del scratch
         torch._foreach_add_([m.num_batches_tracked for m in bn], 1)  # one launch for the 7 counters
         ctx.drop_p, ctx.seed, ctx.b = float(drop_p), int(seed), b
@@ -1235,20 +1039,13 @@ class HardNetTrainFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        lib = load_library()
         saved, *ws_w = ctx.saved_tensors
         dws = [torch.empty_like(w) for w in ws_w]
         need_x = ctx.needs_input_grad[0]
         din = torch.empty((ctx.b, 1, 32, 32), device=dout.device, dtype=torch.float32) if need_x else None
-        _, n_sc = train_workspace_bytes(ctx.b)
-        scratch = torch.empty(n_sc, device=dout.device, dtype=torch.uint8)
-        stream = torch.cuda.current_stream(dout.device).cuda_stream
-        with torch.cuda.device(dout.device):
-            _check(lib.hn_hardnet_train_backward(dout.contiguous().data_ptr(), ctx.b, _ptr_array(ws_w),
-                                                 _ptr_array(dws), din.data_ptr() if din is not None else None,
-                                                 ctx.drop_p, ctx.seed, saved.data_ptr(), saved.numel(),
-                                                 scratch.data_ptr(), scratch.numel(), stream),
-                   "hn_hardnet_train_backward")
+        scratch = torch.empty(train_workspace_bytes(ctx.b)[1], device=dout.device, dtype=torch.uint8)
+        _call(dout.device, "hn_hardnet_train_backward", dout.contiguous(), ctx.b, _ptr_array(ws_w), _ptr_array(dws),
+              din, ctx.drop_p, ctx.seed, *_buf(saved), *_buf(scratch))
         return (din, None, None, None, *dws)
 
 
@@ -1267,13 +1064,14 @@ def supernet_desc(layers=None) -> HnArchDesc:
 def train_tensors(module):
     """The float state_dict tensors the train ABI walks, in order (num_batches_tracked and the
     supernet's thetas left out), as (names, tensors)."""
-    names, ts = [], []
-    for k, v in module.state_dict(keep_vars=True).items():
-        if k.endswith("num_batches_tracked") or k.endswith(".thetas"):
-            continue
-        names.append(k)
-        ts.append(v)
-    return names, ts
+    kept = [(k, v) for k, v in module.state_dict(keep_vars=True).items()
+            if not k.endswith(("num_batches_tracked", ".thetas"))]
+    return [k for k, _ in kept], [v for _, v in kept]
+
+
+def nas_train_workspace_bytes(desc: HnArchDesc, batch: int):
+    """(saved, scratch) bytes of hn_nas_train_forward / _backward for a descriptor and a batch."""
+    return _size("hn_nas_train_workspace_bytes", desc, batch, n=2)
 
 
 class NasTrainFunction(torch.autograd.Function):
@@ -1287,66 +1085,37 @@ class NasTrainFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, soft, desc, tensors, momentum, *params):
-        lib = load_library()
         b = x.shape[0]
-        nt = ctypes.c_size_t()
-        _check(lib.hn_nas_train_tensor_count(ctypes.byref(desc), ctypes.byref(nt)), "hn_nas_train_tensor_count")
-        if len(tensors) != nt.value:
-            raise ValueError(f"the module has {len(tensors)} float state_dict tensors, the descriptor walks {nt.value}")
+        nt = _size("hn_nas_train_tensor_count", desc)
+        if len(tensors) != nt:
+            raise ValueError(f"the module has {len(tensors)} float state_dict tensors, the descriptor walks {nt}")
         if soft is not None:
             n_layers = int(desc.n_layers)
             if tuple(soft.shape) != (n_layers, 17) or soft.device != x.device or soft.dtype != torch.float32:
                 raise ValueError(f"soft must be fp32 [{n_layers}, 17] on {x.device}, got {soft.dtype} "
                                  f"{tuple(soft.shape)} on {soft.device}")
-        sv, sc = ctypes.c_size_t(), ctypes.c_size_t()
-        _check(lib.hn_nas_train_workspace_bytes(ctypes.byref(desc), b, ctypes.byref(sv), ctypes.byref(sc)),
-               "hn_nas_train_workspace_bytes")
-        saved = torch.empty(sv.value, device=x.device, dtype=torch.uint8)
-        scratch = torch.empty(sc.value, device=x.device, dtype=torch.uint8)
+        n_sv, n_sc = nas_train_workspace_bytes(desc, b)
+        saved = torch.empty(n_sv, device=x.device, dtype=torch.uint8)
+        scratch = torch.empty(n_sc, device=x.device, dtype=torch.uint8)
         out = torch.empty((b, 128), device=x.device, dtype=torch.float32)
         soft_c = soft.detach().contiguous() if soft is not None else None
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        with torch.cuda.device(x.device):
-            _check(lib.hn_nas_train_forward(ctypes.byref(desc), x.data_ptr(), b, _ptr_array(tensors), float(momentum),
-                                            soft_c.data_ptr() if soft_c is not None else None, out.data_ptr(),
-                                            saved.data_ptr(), saved.numel(), scratch.data_ptr(), scratch.numel(),
-                                            stream), "hn_nas_train_forward")
+        _call(x.device, "hn_nas_train_forward", desc, x, b, _ptr_array(tensors), float(momentum), soft_c, out,
+              *_buf(saved), *_buf(scratch))
         del scratch
-        ctx.desc, ctx.tensors, ctx.b = desc, tensors, b
-        # per slot: 1 = a parameter whose gradient is returned, 2 = a frozen parameter (the kernels still
-        # write its gradient: it gets a throwaway buffer), 0 = a buffer (running statistics)
-        ctx.slot = [1 if t.requires_grad else 2 if isinstance(t, torch.nn.Parameter) else 0 for t in tensors]
+        ctx.desc, ctx.tensors, ctx.b, ctx.slot = desc, tensors, b, _grad_slots(tensors)
         ctx.has_soft = soft is not None
         ctx.save_for_backward(saved, x, soft_c if soft_c is not None else x.new_empty(0), *params)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        lib = load_library()
         saved, x, soft_c, *params = ctx.saved_tensors
-        # one allocation for every parameter's gradient (the supernet has ~2,000), handed out as views
-        # (contiguous, the parameters' shapes: autograd stores them as .grad without a copy)
-        flat = torch.empty(sum(p.numel() for p in params), device=dout.device, dtype=torch.float32)
-        grads = [g.view(p.shape) for g, p in zip(flat.split([p.numel() for p in params]), params)]
-        it = iter(grads)
-        gptrs = [next(it) if k == 1 else torch.empty_like(t) if k == 2 else None
-                 for k, t in zip(ctx.slot, ctx.tensors)]
-        sv, sc = ctypes.c_size_t(), ctypes.c_size_t()
-        _check(lib.hn_nas_train_workspace_bytes(ctypes.byref(ctx.desc), ctx.b, ctypes.byref(sv), ctypes.byref(sc)),
-               "hn_nas_train_workspace_bytes")
-        scratch = torch.empty(sc.value, device=dout.device, dtype=torch.uint8)
+        grads, bufs = _grad_buffers(params, ctx.slot, ctx.tensors)
+        scratch = torch.empty(nas_train_workspace_bytes(ctx.desc, ctx.b)[1], device=dout.device, dtype=torch.uint8)
         dsoft = torch.empty_like(soft_c) if ctx.has_soft else None
         # the input gradient (conv0's data gradient through input_norm) only when the patches need one
         din = torch.empty((ctx.b, 1, 32, 32), device=dout.device, dtype=torch.float32) \
             if ctx.needs_input_grad[0] else None
-        stream = torch.cuda.current_stream(dout.device).cuda_stream
-        gp = (ctypes.c_void_p * len(gptrs))(*[g.data_ptr() if g is not None else None for g in gptrs])
-        with torch.cuda.device(dout.device):
-            _check(lib.hn_nas_train_backward_dx(ctypes.byref(ctx.desc), dout.contiguous().data_ptr(), x.data_ptr(),
-                                                ctx.b, _ptr_array(ctx.tensors),
-                                                soft_c.data_ptr() if ctx.has_soft else None, gp,
-                                                dsoft.data_ptr() if dsoft is not None else None,
-                                                din.data_ptr() if din is not None else None, saved.data_ptr(),
-                                                saved.numel(), scratch.data_ptr(), scratch.numel(), stream),
-                   "hn_nas_train_backward_dx")
+        _call(dout.device, "hn_nas_train_backward_dx", ctx.desc, dout.contiguous(), x, ctx.b, _ptr_array(ctx.tensors),
+              soft_c if ctx.has_soft else None, _ptr_array(bufs), dsoft, din, *_buf(saved), *_buf(scratch))
         return (din, dsoft, None, None, None, *grads)
