@@ -117,6 +117,8 @@ _PROTOTYPES = {
     "hn_hardnet_train_workspace_bytes": (I64, SP, SP),
     "hn_hardnet_train_forward": (P, I64, PP, PP, PP, F32, F32, U64, P, P, S, P, S, P),
     "hn_hardnet_train_backward": (P, I64, PP, PP, P, F32, U64, P, S, P, S, P),
+    "hn_hardnet_train_layer_op_workspace_bytes": (I32, I32, I64, SP),
+    "hn_hardnet_train_layer_op": (I32, I32, I32, I32, I64, I64, P, P, P, P, P, P, F32, F32, U64, P, S, P),
     "hn_nas_train_tensor_count": (D, SP),
     "hn_nas_train_workspace_bytes": (D, I64, SP, SP),
     "hn_nas_train_forward": (D, P, I64, PP, F32, P, P, P, S, P, S, P),
@@ -1047,6 +1049,27 @@ class HardNetTrainFunction(torch.autograd.Function):
         _call(dout.device, "hn_hardnet_train_backward", dout.contiguous(), ctx.b, _ptr_array(ws_w), _ptr_array(dws),
               din, ctx.drop_p, ctx.seed, *_buf(saved), *_buf(scratch))
         return (din, None, None, None, *dws)
+
+
+TRAIN_OPS = {"input_norm": 0, "conv_fwd": 1, "bn_fwd": 2, "l2_fwd": 3, "l2_bwd": 4, "bn_bwd": 5, "conv_wgrad": 6,
+             "conv_dgrad": 7, "input_norm_bwd": 8}  # enum hn_train_op
+
+
+def train_layer_op_workspace_bytes(batch: int, bits: int = -1, row_segments: int = 0) -> int:
+    return _size("hn_hardnet_train_layer_op_workspace_bytes", bits, row_segments, batch)
+
+
+def train_layer_op(op: str, layer: int, batch: int, x=None, w=None, y=None, aux=(None, None, None), bits: int = -1,
+                   row_segments: int = 0, dgrad_chunk: int = 0, momentum: float = 0.1, dropout_p: float = 0.0,
+                   seed: int = 0, scratch=None):
+    """One layer operation of the HardNet train step on caller-owned CNHW buffers (hn_hardnet_train_layer_op, a test
+    and diagnostic entry; the header's table gives each operation's x / w / y / aux).  Nothing is allocated but the
+    scratch, when none is given."""
+    need = train_layer_op_workspace_bytes(batch, bits, row_segments)
+    scratch = _workspace(scratch, need, y.device, "scratch", too_small="raise")
+    _call(y.device, "hn_hardnet_train_layer_op", TRAIN_OPS[op], layer, bits, row_segments, dgrad_chunk, batch, x, w, y,
+          *aux, momentum, dropout_p, seed, *_buf(scratch))
+    return y
 
 
 # ----------------------------------------------------------------------------------

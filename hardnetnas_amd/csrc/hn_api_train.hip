@@ -61,6 +61,60 @@ extern "C" int hn_hardnet_train_backward(const float* d_dout, int64_t batch, con
   return HN_OK;
 }
 
+// one layer operation of the step alone (a test and diagnostic entry: the header's table gives each operation's
+// buffers)
+static int layer_op_config(int32_t bits, int32_t row_segments, int64_t batch) {
+  if (batch < 2 || batch > (1 << 24)) return fail(HN_ERR_ARG, "batch must be 2 .. 2^24");
+  if (bits < -1 || bits > 255) return fail(HN_ERR_ARG, "train_f32_bits must be -1 (the process's) or 0 .. 255");
+  if (row_segments != 0 && row_segments != 1 && row_segments != 2 && row_segments != 4)
+    return fail(HN_ERR_ARG, "row_segments must be 0, 1, 2 or 4");
+  return HN_OK;
+}
+
+extern "C" int hn_hardnet_train_layer_op_workspace_bytes(int32_t train_f32_bits, int32_t row_segments, int64_t batch,
+                                                         size_t* scratch_bytes_out) {
+  if (!scratch_bytes_out) return fail(HN_ERR_ARG, "NULL scratch_bytes_out");
+  if (int rc = layer_op_config(train_f32_bits, row_segments, batch)) return rc;
+  *scratch_bytes_out = hn_train_layout((long)batch, train_f32_bits, row_segments).scratch_total;
+  return HN_OK;
+}
+
+extern "C" int hn_hardnet_train_layer_op(int32_t op, int32_t layer, int32_t train_f32_bits, int32_t row_segments,
+                                         int64_t dgrad_chunk, int64_t batch, const float* d_x, const float* d_w,
+                                         float* d_y, float* d_aux0, float* d_aux1, float* d_aux2, float momentum,
+                                         float dropout_p, uint64_t seed, void* d_scratch, size_t scratch_bytes,
+                                         void* hip_stream) {
+  size_t need = 0;
+  if (int rc = hn_hardnet_train_layer_op_workspace_bytes(train_f32_bits, row_segments, batch, &need)) return rc;
+  if (op < HN_TRAIN_OP_INPUT_NORM || op > HN_TRAIN_OP_INPUT_NORM_BWD)
+    return fail(HN_ERR_ARG, "unknown op " + std::to_string(op));
+  if (layer < 0 || layer > 6) return fail(HN_ERR_ARG, "layer must be 0 .. 6");
+  const int form = hn_train_conv_form(op, layer, train_f32_bits < 0 ? hn_knobs().train_f32 : train_f32_bits);
+  if (row_segments && form != kHnFormRing && form != kHnFormRingShared)
+    return fail(HN_ERR_ARG, "row_segments: this op / layer / train_f32_bits has no row-segment kernel");
+  if (dgrad_chunk < 0 || dgrad_chunk > batch) return fail(HN_ERR_ARG, "dgrad_chunk must be 0 .. batch");
+  if (dgrad_chunk && !(op == HN_TRAIN_OP_CONV_DGRAD && form == kHnFormCol))
+    return fail(HN_ERR_ARG, "dgrad_chunk: this op / layer / train_f32_bits is not the column-GEMM data gradient");
+  const bool needs_x = op != HN_TRAIN_OP_BN_FWD;
+  const bool needs_w = op == HN_TRAIN_OP_CONV_FWD || op == HN_TRAIN_OP_L2_BWD || op == HN_TRAIN_OP_BN_BWD ||
+                       op == HN_TRAIN_OP_CONV_WGRAD || op == HN_TRAIN_OP_CONV_DGRAD;
+  const bool needs_aux0 = op == HN_TRAIN_OP_INPUT_NORM || op == HN_TRAIN_OP_BN_FWD || op == HN_TRAIN_OP_INPUT_NORM_BWD;
+  if (!d_y || (needs_x && !d_x) || (needs_w && !d_w) || (needs_aux0 && !d_aux0))
+    return fail(HN_ERR_ARG, "NULL device pointer");
+  if (op == HN_TRAIN_OP_BN_FWD)
+    if (int rc = hn_pair_given(d_aux1, d_aux2, "running_mean and running_var")) return rc;
+  if (!(dropout_p >= 0.f && dropout_p < 1.f)) return fail(HN_ERR_ARG, "dropout_p must be in [0, 1)");
+  if (hn_misaligned(16, d_x, d_w, d_y, d_aux0, d_aux1, d_aux2, static_cast<const char*>(d_scratch)))
+    return fail(HN_ERR_ARG, "device pointers must be 16-byte aligned");
+  if (!d_scratch) return fail(HN_ERR_ARG, "NULL workspace");
+  if (int rc = hn_need_ws(scratch_bytes, need, "scratch ")) return rc;
+  const HnTrainOpArgs o{op,    layer,  train_f32_bits, row_segments, (long)dgrad_chunk, (long)batch, d_x,   d_w,
+                        d_y,   d_aux0, d_aux1,         d_aux2,       momentum,          dropout_p,   1e-5f, 1e-7f,
+                        1e-10f, (unsigned long long)seed};
+  HIPCHK(hn_train_layer_op(o, static_cast<char*>(d_scratch), static_cast<hipStream_t>(hip_stream)));
+  return HN_OK;
+}
+
 // ---------------------------------------------------------------------------------------
 // train-mode hardnetNAS (hn_nas_train.hip)
 // ---------------------------------------------------------------------------------------

@@ -395,7 +395,29 @@ struct HnTrainWs {  // byte offsets into the train workspace's saved region (xn 
   size_t xn, inv_sd, z[7], rstd[7], saved_total;
   size_t g0, g1, col, part, bnpart, bnmean, wt, nhwc0, nhwc1, wpack, zero, scratch_total;
 };
-HnTrainWs hn_train_layout(long B);
+HnTrainWs hn_train_layout(long B, int tf = -1, int ns = 0);  // tf < 0: the process's HN_TRAIN_F32 bits
+// one layer operation of the step on caller-owned buffers (hn_hardnet_train_layer_op): the form of a convolution
+// operation under the HN_TRAIN_F32 bits `tf` (-1: not a convolution operation), and the call itself
+enum HnConvForm {
+  kHnFormDirect0,     // conv0: k_fwd0 / k_wgrad0
+  kHnFormBf16x3,      // the inference bf16x3 conv kernels over NHWC
+  kHnFormRing,        // one LDS ring per wave: k_fwd3 / k_fwd2 / k_dgrad2 / k_wgrad3 / k_wgrad2 (row segments)
+  kHnFormRingShared,  // one LDS ring per patch: k_fwd3s / k_fwd2 / k_dgrad2 with NWP > 1 (row segments)
+  kHnFormGemm,        // the generic implicit GEMM
+  kHnFormCol          // the column GEMM + col2im / conv6's transpose (patch chunks)
+};
+int hn_train_conv_form(int op, int layer, int tf);
+struct HnTrainOpArgs {
+  int op, layer, tf, ns;
+  long chunk, B;
+  const float* x;
+  const float* w;
+  float* y;
+  float *aux0, *aux1, *aux2;
+  float mom, drop_p, bn_eps, in_eps, l2_eps;
+  unsigned long long seed;
+};
+hipError_t hn_train_layer_op(const HnTrainOpArgs& o, char* scratch, hipStream_t st);
 // train-mode hardnetNAS (hn_nas_train.hip): tensors consumed, saved / scratch workspace bytes
 int hn_nas_train_plan(const hn_arch_desc& d, long B, size_t* n_tensors, size_t* saved, size_t* scratch);
 int hn_nas_train_null_grad_slot(const hn_arch_desc& d, float* const* grads);

@@ -242,9 +242,9 @@ __global__ __launch_bounds__(256) void k_wgrad3(const float* __restrict__ zx, co
 static int wgrad3_ns(long B) { return B >= 2048 ? 1 : B >= 1024 ? 2 : 4; }  // (B x NS waves per layer)
 
 template <int CIN, int COUT, int H>
-hipError_t wgrad3(const float* zx, const float* dY, long B, float* dW, float* part, hipStream_t st) {
+hipError_t wgrad3(const float* zx, const float* dY, long B, float* dW, float* part, hipStream_t st, int ns_over) {
   using C = Wg3Cfg<CIN, COUT, H>;
-  const int ns = wgrad3_ns(B);
+  const int ns = ns_over ? ns_over : wgrad3_ns(B);
   const long chunks = (B * ns + C::NPC - 1) / C::NPC;
   auto go = [&](auto nsc) {
     constexpr int NS = decltype(nsc)::value;
@@ -263,9 +263,9 @@ hipError_t wgrad3(const float* zx, const float* dY, long B, float* dW, float* pa
 }
 
 // slices k_wgrad3 writes for layer l (0 if it does not take that layer)
-static long wgrad3_slices(int l, long B) {
+static long wgrad3_slices(int l, long B, int ns_over) {
   const int npc = l == 1 ? Wg3Cfg<32, 32, 32>::NPC : l == 3 ? Wg3Cfg<64, 64, 16>::NPC : l == 5 ? Wg3Cfg<128, 128, 8>::NPC : 0;
-  return npc ? (B * wgrad3_ns(B) + npc - 1) / npc : 0;  // one slice per workgroup chunk
+  return npc ? (B * (ns_over ? ns_over : wgrad3_ns(B)) + npc - 1) / npc : 0;  // one slice per workgroup chunk
 }
 
 // ------------------------------------------------------------------------------------------
@@ -506,9 +506,9 @@ __global__ __launch_bounds__(256) void k_fwd3s(const float* __restrict__ zx, int
 static int fwd3_ns(long waves) { return waves >= 2048 ? 1 : waves >= 1024 ? 2 : 4; }
 
 template <int CIN, int COUT, int H>
-hipError_t fwd3s(const float* zx, bool relu, const float* W, long B, float* z, hipStream_t st) {
+hipError_t fwd3s(const float* zx, bool relu, const float* W, long B, float* z, hipStream_t st, int ns_over) {
   constexpr int NWP = COUT / 32, PPB = 4 / NWP;
-  const int ns = std::min(fwd3_ns(B * NWP), H / Fw3Cfg<CIN, COUT, H>::G);
+  const int ns = std::min(ns_over ? ns_over : fwd3_ns(B * NWP), H / Fw3Cfg<CIN, COUT, H>::G);
   auto go = [&](auto nsc) {
     constexpr int NS = decltype(nsc)::value;
     hipLaunchKernelGGL((k_fwd3s<CIN, COUT, H, NWP, NS>), dim3((unsigned)((B * NS + PPB - 1) / PPB)), dim3(256), 0, st,
@@ -541,8 +541,8 @@ __global__ __launch_bounds__(256) void k_wflip(const float* __restrict__ w, int 
 }
 
 template <int CIN, int COUT, int H>
-hipError_t fwd3(const float* zx, bool relu, const float* W, long B, float* z, hipStream_t st) {
-  const int ns = std::min(fwd3_ns(B), H / Fw3Cfg<CIN, COUT, H>::G);
+hipError_t fwd3(const float* zx, bool relu, const float* W, long B, float* z, hipStream_t st, int ns_over) {
+  const int ns = std::min(ns_over ? ns_over : fwd3_ns(B), H / Fw3Cfg<CIN, COUT, H>::G);
   auto go = [&](auto nsc) {
     constexpr int NS = decltype(nsc)::value;
     hipLaunchKernelGGL((k_fwd3<CIN, COUT, H, NS>), dim3((unsigned)((B * NS + 3) / 4)), dim3(256), 0, st, zx,
@@ -715,10 +715,11 @@ static void launch_ns(int ns, F&& go) {
 }
 
 template <int CIN, int COUT, int HI, int NWP = (COUT / 32 >= 4 ? 4 : COUT / 32)>
-hipError_t fwd2(const float* zx, bool relu, const float* W, long B, float* z, hipStream_t st, bool shared) {
+hipError_t fwd2(const float* zx, bool relu, const float* W, long B, float* z, hipStream_t st, bool shared,
+                int ns_over) {
   using C = Fw2Cfg<CIN, COUT, HI>;
   const int nwp = shared ? NWP : 1;
-  launch_ns<C::HO, C::G>(fwd3_ns(B * nwp), [&](auto nsc) {
+  launch_ns<C::HO, C::G>(ns_over ? ns_over : fwd3_ns(B * nwp), [&](auto nsc) {
     constexpr int NS = decltype(nsc)::value;
     if (shared)
       hipLaunchKernelGGL((k_fwd2<CIN, COUT, HI, NWP, NS>), dim3((unsigned)((B * NS + 4 / NWP - 1) / (4 / NWP))),
@@ -861,11 +862,11 @@ __global__ __launch_bounds__(256) void k_dgrad2(const float* __restrict__ dY, co
 }
 
 template <int CO, int CI, int HO>
-hipError_t dgrad2(const float* dY, const float* W, long B, float* din, hipStream_t st, bool shared) {
+hipError_t dgrad2(const float* dY, const float* W, long B, float* din, hipStream_t st, bool shared, int ns_over) {
   constexpr int NWP = CI / 32 >= 4 ? 4 : CI / 32;
   using C = Dg2Cfg<CO, CI, HO>;
   const bool sh = shared && NWP > 1;
-  launch_ns<HO, C::G>(fwd3_ns(B * (sh ? NWP : 1)), [&](auto nsc) {
+  launch_ns<HO, C::G>(ns_over ? ns_over : fwd3_ns(B * (sh ? NWP : 1)), [&](auto nsc) {
     constexpr int NS = decltype(nsc)::value;
     if (sh)
       hipLaunchKernelGGL((k_dgrad2<CO, CI, HO, NWP, NS>), dim3((unsigned)((B * NS + 4 / NWP - 1) / (4 / NWP))),
@@ -994,9 +995,9 @@ __global__ __launch_bounds__(256) void k_wgrad2(const float* __restrict__ zx, co
 }
 
 template <int CIN, int COUT, int HO>
-hipError_t wgrad2(const float* zx, const float* dY, long B, float* dW, float* part, hipStream_t st) {
+hipError_t wgrad2(const float* zx, const float* dY, long B, float* dW, float* part, hipStream_t st, int ns_over) {
   using C = Wg2Cfg<CIN, COUT, HO>;
-  const int ns = wgrad3_ns(B);
+  const int ns = ns_over ? ns_over : wgrad3_ns(B);
   const long chunks = (B * ns + C::NPC - 1) / C::NPC;
   auto go = [&](auto nsc) {
     constexpr int NS = decltype(nsc)::value;
@@ -1015,15 +1016,15 @@ hipError_t wgrad2(const float* zx, const float* dY, long B, float* dW, float* pa
 }
 
 
-static long wgrad2_slices(int l, long B) {
+static long wgrad2_slices(int l, long B, int ns_over) {
   const int npc = l == 2 ? Wg2Cfg<32, 64, 16>::NPC : l == 4 ? Wg2Cfg<64, 128, 8>::NPC : 0;
-  return npc ? (B * wgrad3_ns(B) + npc - 1) / npc : 0;  // one slice per workgroup chunk
+  return npc ? (B * (ns_over ? ns_over : wgrad3_ns(B)) + npc - 1) / npc : 0;  // one slice per workgroup chunk
 }
 
 // implicit-im2col convs of one layer (compile-time geometry): the forward Y = W . col and the
 // weight gradient dW = dY . col^T over the whole batch, with no column matrix in memory
 template <int C, int H, int KS, int S, int PAD>
-hipError_t conv_fwd(const ActIn& a, long B, const float* W, int cout, float* z, float* part, hipStream_t st) {
+hipError_t gemm_fwd(const ActIn& a, long B, const float* W, int cout, float* z, float* part, hipStream_t st) {
   using L = Im2colB<C, H, KS, S, PAD, false>;
   const long n = B * L::HWO, K = (long)C * KS * KS;
   GemmArgs g{W, nullptr, z, cout, n, K, K, 1, 2, 1, n, 1, 1.f, 0.f};  // B contiguous along N
@@ -1031,7 +1032,7 @@ hipError_t conv_fwd(const ActIn& a, long B, const float* W, int cout, float* z, 
 }
 // dX [C][B H H] = Wt [C][COUT KK] . col2im-gather(dY), Wt transposed into `wt` first
 template <int C, int H, int KS, int S, int PAD>
-hipError_t conv_dgrad(const float* dY, long B, const float* W, int cout, float* wt, float* dX, hipStream_t st) {
+hipError_t gemm_dgrad(const float* dY, long B, const float* W, int cout, float* wt, float* dX, hipStream_t st) {
   constexpr int KK = KS * KS;
   const long nw = (long)cout * C * KK;
   hipLaunchKernelGGL(k_wt, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, st, W, cout, C, KK, wt);
@@ -1046,7 +1047,7 @@ hipError_t conv_dgrad(const float* dY, long B, const float* W, int cout, float* 
   return gemm(g, st, nullptr, Col2imB<128, H, KS, S, PAD>{dY, B});
 }
 template <int C, int H, int KS, int S, int PAD>
-hipError_t conv_wgrad(const ActIn& a, long B, const float* dY, int cout, float* dW, float* part, hipStream_t st) {
+hipError_t gemm_wgrad(const ActIn& a, long B, const float* dY, int cout, float* dW, float* part, hipStream_t st) {
   using L = Im2colB<C, H, KS, S, PAD, true>;
   const long n = B * L::HWO, K = (long)C * KS * KS;
   GemmArgs g{dY, nullptr, dW, cout, K, n, n, 1, 1, 2, K, 1, 1.f, 0.f};  // B contiguous along K (= pos)
@@ -1055,26 +1056,26 @@ hipError_t conv_wgrad(const ActIn& a, long B, const float* dY, int cout, float* 
 #define HN_TRAIN_LAYERS(X) \
   X(0, 1, 32, 3, 1, 1) X(1, 32, 32, 3, 1, 1) X(2, 32, 32, 3, 2, 1) X(3, 64, 16, 3, 1, 1) X(4, 64, 16, 3, 2, 1) \
   X(5, 128, 8, 3, 1, 1) X(6, 128, 8, 8, 1, 0)
-hipError_t conv_fwd_l(int l, const ActIn& a, long B, const float* W, int cout, float* z, float* part,
+hipError_t gemm_fwd_l(int l, const ActIn& a, long B, const float* W, int cout, float* z, float* part,
                       hipStream_t st) {
 #define HN_F(L_, C, H, KS, S, PAD) \
-  if (l == L_) return conv_fwd<C, H, KS, S, PAD>(a, B, W, cout, z, part, st);
+  if (l == L_) return gemm_fwd<C, H, KS, S, PAD>(a, B, W, cout, z, part, st);
   HN_TRAIN_LAYERS(HN_F)
 #undef HN_F
   return hipErrorInvalidValue;
 }
-hipError_t conv_wgrad_l(int l, const ActIn& a, long B, const float* dY, int cout, float* dW, float* part,
+hipError_t gemm_wgrad_l(int l, const ActIn& a, long B, const float* dY, int cout, float* dW, float* part,
                         hipStream_t st) {
 #define HN_W(L_, C, H, KS, S, PAD) \
-  if (l == L_) return conv_wgrad<C, H, KS, S, PAD>(a, B, dY, cout, dW, part, st);
+  if (l == L_) return gemm_wgrad<C, H, KS, S, PAD>(a, B, dY, cout, dW, part, st);
   HN_TRAIN_LAYERS(HN_W)
 #undef HN_W
   return hipErrorInvalidValue;
 }
-hipError_t conv_dgrad_l(int l, const float* dY, long B, const float* W, int cout, float* wt, float* dX,
+hipError_t gemm_dgrad_l(int l, const float* dY, long B, const float* W, int cout, float* wt, float* dX,
                         hipStream_t st) {
 #define HN_D(L_, C, H, KS, S, PAD) \
-  if (l == L_) return conv_dgrad<C, H, KS, S, PAD>(dY, B, W, cout, wt, dX, st);
+  if (l == L_) return gemm_dgrad<C, H, KS, S, PAD>(dY, B, W, cout, wt, dX, st);
   HN_TRAIN_LAYERS(HN_D)
 #undef HN_D
   return hipErrorInvalidValue;
@@ -1100,7 +1101,10 @@ static long chunk_of(const HnTrainLayer& l, long B) {
   return std::max<long>(1, std::min<long>(B, (long)(kColBudget / per)));
 }
 
-HnTrainWs hn_train_layout(long B) {
+// tf: the HN_TRAIN_F32 bits the layout serves (< 0: the process's); ns: a row-segment override of the ring weight
+// gradients (0: by batch), which sizes their split-K slices in `part`
+HnTrainWs hn_train_layout(long B, int tf, int ns) {
+  if (tf < 0) tf = hn_knobs().train_f32;
   // Two regions.  "saved" holds what the backward reads (one per forward call: autograd keeps it
   // until the backward has run); "scratch" is transient (the caller may reuse it between calls).
   HnTrainWs w{};
@@ -1141,7 +1145,7 @@ HnTrainWs hn_train_layout(long B) {
   part = std::max(part, (size_t)32 * 9 * wgrad0_slices(B) * 4);  // k_wgrad0's slices
   for (int l = 1; l <= 5; ++l) {  // k_wgrad3's / k_wgrad2's slices
     const HnTrainLayer& L = kHardnetTrainLayers[l];
-    part = std::max(part, (size_t)L.cout * L.cin * 9 * (wgrad3_slices(l, B) + wgrad2_slices(l, B)) * 4);
+    part = std::max(part, (size_t)L.cout * L.cin * 9 * (wgrad3_slices(l, B, ns) + wgrad2_slices(l, B, ns)) * 4);
   }
   w.part = take(part);
   w.bnpart = take((size_t)128 * kBnSlices * 2 * sizeof(double));
@@ -1149,7 +1153,7 @@ HnTrainWs hn_train_layout(long B) {
   w.bnmean = take((size_t)2 * 128 * sizeof(float));
   // the bf16x3 conv path (HN_TRAIN_F32 bit 0 or 1 off): NHWC in / out (the largest activation:
   // 32 x 32 x 32 per patch), one packed layer (conv5: 128 x 128 x 9 x 2 bf16 pairs), a zero bias
-  const bool bf16x3 = (hn_knobs().train_f32 & 3) != 3;
+  const bool bf16x3 = (tf & 3) != 3;
   w.nhwc0 = take(bf16x3 ? (size_t)B * 32 * 1024 * 4 : 0);
   w.nhwc1 = take(bf16x3 ? (size_t)B * 32 * 1024 * 4 : 0);
   w.wpack = take(bf16x3 ? (size_t)128 * 128 * 9 * 2 * 2 * 2 : 0);
@@ -1186,154 +1190,241 @@ static hipError_t conv_bf16x3(int l, bool flip, const float* x, bool relu, long 
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------
+// The step, one layer operation at a time.  Each function is the only code path of its operation: the two step
+// functions below are loops over them (with the process's HN_TRAIN_F32 bits and no overrides), and
+// hn_train_layer_op runs one alone on caller-owned buffers.  tf: the HN_TRAIN_F32 bits (hn_internal.h); ns: a
+// row-segment override of the ring kernels (0: by batch; else 1, 2 or 4, clamped to the kernel's whole steps per
+// patch); chunk: patches per column chunk of the column-GEMM data gradient (0: chunk_of).
+// ------------------------------------------------------------------------------------------
+int hn_train_conv_form(int op, int l, int tf) {
+  const bool s1 = l == 1 || l == 3 || l == 5, s2 = l == 2 || l == 4;
+  if (op == HN_TRAIN_OP_CONV_FWD) {
+    if (l == 0) return !(tf & 64) ? kHnFormDirect0 : kHnFormGemm;
+    if (l <= 5 && !(tf & 1)) return kHnFormBf16x3;
+    // conv3 / conv5 default to the shared ring; conv2: one ring per wave (shared by 2 waves measured 0.64 vs
+    // 0.31 ms); conv4: one ring per two waves (one per wave needs 128 prefetch registers per lane and spills)
+    if (s1 && !(tf & 8)) return l == 1 || (tf & 128) ? kHnFormRing : kHnFormRingShared;
+    if (s2 && !(tf & 32)) return (l == 2) == ((tf & 128) != 0) ? kHnFormRingShared : kHnFormRing;
+    return kHnFormGemm;
+  }
+  if (op == HN_TRAIN_OP_CONV_WGRAD) {
+    if (l == 0) return !(tf & 64) ? kHnFormDirect0 : kHnFormGemm;
+    if (s1 && !(tf & 4)) return kHnFormRing;
+    if (s2 && !(tf & 32)) return kHnFormRing;
+    return kHnFormGemm;
+  }
+  if (op == HN_TRAIN_OP_CONV_DGRAD) {
+    if (l == 0) return kHnFormGemm;
+    // stride-1 3x3 (Cin = Cout): k_fwd3 over dY with the flipped weights, else the same conv on the bf16x3 MFMA
+    // conv kernels, else the implicit col2im-gather GEMM
+    if (s1 && !(tf & 16)) return l == 1 || (tf & 128) ? kHnFormRing : kHnFormRingShared;
+    if (s1) return !(tf & 2) ? kHnFormBf16x3 : kHnFormGemm;
+    // stride-2 3x3: k_dgrad2 (conv2's 32 input channels are one block: never shared), else the column GEMM + col2im
+    if (s2 && !(tf & 32)) return l == 4 && !(tf & 128) ? kHnFormRingShared : kHnFormRing;
+    return kHnFormCol;  // and the 8x8 conv6 (one tap per pixel)
+  }
+  return -1;
+}
+
+static hipError_t input_norm(const float* in, long B, float in_eps, float* xn, float* inv_sd, hipStream_t st) {
+  hipLaunchKernelGGL(k_input_norm, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, in, B, in_eps, xn, inv_sd);
+  return hipGetLastError();
+}
+
+// z_l = conv_l(a): a = the normalised patch, or relu(z) of the previous layer (x the dropout mask before conv6,
+// HardNet.py:299)
+static hipError_t conv_fwd(int l, int tf, int ns, const ActIn& a, const float* W, long B, float* z, char* sc,
+                           const HnTrainWs& L, hipStream_t st) {
+  const HnTrainLayer& S = kHardnetTrainLayers[l];
+  const int form = hn_train_conv_form(HN_TRAIN_OP_CONV_FWD, l, tf);
+  const bool sh = form == kHnFormRingShared;
+  if (form == kHnFormDirect0) {  // conv0: k_fwd0 (taps as the MFMA's K)
+    hipLaunchKernelGGL(k_fwd0, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, a.z, W, B, z);
+    return hipGetLastError();
+  }
+  if (form == kHnFormBf16x3) return conv_bf16x3(l, false, a.z, true, B, W, z, sc, L, st);
+  if (form == kHnFormGemm)  // Y = W . im2col(a)
+    return gemm_fwd_l(l, a, B, W, S.cout, z, reinterpret_cast<float*>(sc + L.part), st);
+  if (l == 1) return fwd3<32, 32, 32>(a.z, true, W, B, z, st, ns);  // stride-1 3x3: k_fwd3 (f32 MFMA)
+  if (l == 3) return (sh ? fwd3s<64, 64, 16> : fwd3<64, 64, 16>)(a.z, true, W, B, z, st, ns);
+  if (l == 5) return (sh ? fwd3s<128, 128, 8> : fwd3<128, 128, 8>)(a.z, true, W, B, z, st, ns);
+  if (l == 2) return fwd2<32, 64, 32>(a.z, true, W, B, z, st, sh, ns);  // stride-2 3x3: k_fwd2 (f32 MFMA)
+  if (l == 4) return fwd2<64, 128, 16, 2>(a.z, true, W, B, z, st, sh, ns);
+  return hipErrorInvalidValue;
+}
+
+// BatchNorm2d(affine=False), train mode, in place over layer l's conv output; saves rstd, updates the running
+// statistics if given
+static hipError_t bn_fwd(int l, float* z, long B, float* rmean, float* rvar, float mom, float bn_eps, float* rstd,
+                         char* sc, const HnTrainWs& L, hipStream_t st) {
+  const HnTrainLayer& S = kHardnetTrainLayers[l];
+  const long ho = hout_of(S), hw = ho * ho;
+  const int NS = bn_slices(S.cout, B * hw);
+  double* part = reinterpret_cast<double*>(sc + L.bnpart);
+  hipLaunchKernelGGL(k_bn_part, dim3(S.cout, NS), dim3(256), 0, st, z, B * hw, NS, part);
+  hipLaunchKernelGGL(k_bn_apply, bn_row_grid(S.cout, B * hw), dim3(256), 0, st, z, B * hw, part, NS, bn_eps, mom,
+                     rmean, rvar, rstd);
+  return hipGetLastError();
+}
+
+static hipError_t l2_fwd(const float* z6, long B, float l2_eps, float* out, hipStream_t st) {
+  hipLaunchKernelGGL(k_l2_fwd, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, z6, B, l2_eps, out);
+  return hipGetLastError();
+}
+
+static hipError_t l2_bwd(const float* z6, const float* dout, long B, float l2_eps, float* g, hipStream_t st) {
+  hipLaunchKernelGGL(k_l2_bwd, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, z6, dout, B, l2_eps, g);
+  return hipGetLastError();
+}
+
+// g: the gradient w.r.t. layer l's output activation (a_6 = z_6 into the L2 norm; a_5 = dropout(relu(z_5));
+// a_l = relu(z_l) below) -> in place w.r.t. its conv output
+static hipError_t bn_bwd(int l, float* g, const float* zl, const float* rstd, long B, float drop_p,
+                         unsigned long long seed, char* sc, const HnTrainWs& L, hipStream_t st) {
+  const HnTrainLayer& S = kHardnetTrainLayers[l];
+  const long ho = hout_of(S), hw = ho * ho;
+  const int NS = bn_slices(S.cout, B * hw);
+  double* part = reinterpret_cast<double*>(sc + L.bnpart);
+  hipLaunchKernelGGL(k_bn_bwd_part, dim3(S.cout, NS), dim3(256), 0, st, g, zl, B * hw, NS, l < 6 ? 1 : 0,
+                     l == 5 ? drop_p : 0.f, seed, part);
+  hipLaunchKernelGGL(k_bn_bwd_apply, bn_row_grid(S.cout, B * hw), dim3(256), 0, st, g, zl, B * hw, part, NS, rstd,
+                     l < 6 ? 1 : 0, l == 5 ? drop_p : 0.f, seed);
+  return hipGetLastError();
+}
+
+// dW [Cout][K] = dY [Cout][B hw] . im2col(a)^T (split-K slices summed in fp64); a as conv_fwd's
+static hipError_t conv_wgrad(int l, int tf, int ns, const ActIn& a, const float* g, long B, float* dW, char* sc,
+                             const HnTrainWs& L, hipStream_t st) {
+  const HnTrainLayer& S = kHardnetTrainLayers[l];
+  const int form = hn_train_conv_form(HN_TRAIN_OP_CONV_WGRAD, l, tf);
+  float* part = reinterpret_cast<float*>(sc + L.part);
+  if (form == kHnFormDirect0) {  // conv0: k_wgrad0 (taps as the MFMA's N)
+    const long nsl = wgrad0_slices(B);
+    hipLaunchKernelGGL(k_wgrad0, dim3((unsigned)(nsl / 4)), dim3(256), 0, st, a.z, g, B, part);
+    HCK(hipGetLastError());
+    GemmArgs gs{nullptr, nullptr, dW, 32, 9, 0, 0, 0, 0, 0, 9, 1, 1.f, 0.f};
+    hipLaunchKernelGGL(k_splitk_sum, dim3((unsigned)((32 * 9 + 63) / 64)), dim3(1024), 0, st, gs, (int)nsl, part);
+    return hipGetLastError();
+  }
+  if (form == kHnFormGemm) return gemm_wgrad_l(l, a, B, g, S.cout, dW, part, st);
+  if (l == 1) return wgrad3<32, 32, 32>(a.z, g, B, dW, part, st, ns);  // stride-1 3x3: k_wgrad3
+  if (l == 3) return wgrad3<64, 64, 16>(a.z, g, B, dW, part, st, ns);
+  if (l == 5) return wgrad3<128, 128, 8>(a.z, g, B, dW, part, st, ns);
+  if (l == 2) return wgrad2<32, 64, 16>(a.z, g, B, dW, part, st, ns);  // stride-2 3x3: k_wgrad2
+  if (l == 4) return wgrad2<64, 128, 8>(a.z, g, B, dW, part, st, ns);
+  return hipErrorInvalidValue;
+}
+
+// gin: the gradient w.r.t. this layer's input activation, from g w.r.t. its conv output
+static hipError_t conv_dgrad(int l, int tf, int ns, long chunk, const float* g, const float* W, long B, float* gin,
+                             char* sc, const HnTrainWs& L, hipStream_t st) {
+  const HnTrainLayer& S = kHardnetTrainLayers[l];
+  const long ho = hout_of(S), hw = ho * ho, K = (long)S.cin * S.ks * S.ks;
+  const int form = hn_train_conv_form(HN_TRAIN_OP_CONV_DGRAD, l, tf);
+  const bool sh = form == kHnFormRingShared;
+  if (form == kHnFormBf16x3) return conv_bf16x3(l, true, g, false, B, W, gin, sc, L, st);
+  if (form == kHnFormGemm)  // d a_{l-1} [Cin][B H H] = implicit col2im-gather GEMM Wt . dY (every tap lands)
+    return gemm_dgrad_l(l, g, B, W, S.cout, reinterpret_cast<float*>(sc + L.wt), gin, st);
+  if (form == kHnFormCol) {
+    // stride 2 (3 of 4 taps miss a given input pixel) and the 8x8 conv6 (one tap per pixel):
+    // dcol [K][n hw] = W^T [K][Cout] . dY, then the gather col2im, in chunks of patches
+    float* col = reinterpret_cast<float*>(sc + L.col);
+    const long nc = chunk ? std::min(chunk, chunk_of(S, B)) : chunk_of(S, B);
+    for (long n0 = 0; n0 < B; n0 += nc) {
+      const long n = std::min(nc, B - n0);
+      GemmArgs gd{W, g + n0 * hw, col, K, n * hw, S.cout, 1, K, B * hw, 1, n * hw, 1, 1.f, 0.f};
+      HCK(gemm(gd, st));
+      if (S.ks == 8 && ho == 1)  // conv6: the column matrix is the gradient, transposed
+        hipLaunchKernelGGL(k_col6_to_cnhw, dim3(S.cin, (unsigned)((n + 63) / 64)), dim3(256), 0, st, col, B, n0,
+                           n, gin);
+      else
+        hipLaunchKernelGGL(k_col2im, dim3(grid_for((long)S.cin * n * S.hin * S.hin)), dim3(256), 0, st, col,
+                           S.cin, B, S.hin, S.hin, S.ks, S.s, S.pad, (int)ho, (int)ho, n0, n, gin);
+      HCK(hipGetLastError());
+    }
+    return hipSuccess;
+  }
+  if (l == 2) return dgrad2<64, 32, 16>(g, W, B, gin, st, sh, ns);  // k_dgrad2 (the parity classes' taps only)
+  if (l == 4) return dgrad2<128, 64, 8>(g, W, B, gin, st, sh, ns);
+  // stride-1 3x3: k_fwd3 over dY with the flipped weights
+  float* wf = reinterpret_cast<float*>(sc + L.wt);
+  hipLaunchKernelGGL(k_wflip, dim3((unsigned)((S.cout * S.cin * 9 + 255) / 256)), dim3(256), 0, st, W, S.cout, S.cin,
+                     wf);
+  HCK(hipGetLastError());
+  if (l == 1) return fwd3<32, 32, 32>(g, false, wf, B, gin, st, ns);
+  if (l == 3) return (sh ? fwd3s<64, 64, 16> : fwd3<64, 64, 16>)(g, false, wf, B, gin, st, ns);
+  if (l == 5) return (sh ? fwd3s<128, 128, 8> : fwd3<128, 128, 8>)(g, false, wf, B, gin, st, ns);
+  return hipErrorInvalidValue;
+}
+
+// input_norm with detached mean / std (HardNet.py:309-310): d input = d xn / (std + eps), g scaled in place
+static hipError_t input_norm_bwd(float* g, const float* inv_sd, long B, float* din, hipStream_t st) {
+  hipLaunchKernelGGL(k_scale_rows, dim3(grid_for(B * 1024)), dim3(256), 0, st, g, B, inv_sd);
+  HCK(hipGetLastError());
+  return hipMemcpyAsync(din, g, (size_t)B * 1024 * 4, hipMemcpyDeviceToDevice, st);
+}
+
 hipError_t hn_train_forward(const float* in, long B, const float* const* W, float* const* rmean, float* const* rvar,
                             float mom, float bn_eps, float in_eps, float l2_eps, float drop_p,
                             unsigned long long seed, float* out, char* sv, char* sc, hipStream_t st) {
   const HnTrainWs L = hn_train_layout(B);
+  const int tf = hn_knobs().train_f32;
   HCK(hipMemsetAsync(sc + L.zero, 0, 128 * sizeof(float), st));  // the bf16x3 convs' zero bias
   float* xn = reinterpret_cast<float*>(sv + L.xn);
-  hipLaunchKernelGGL(k_input_norm, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, in, B, in_eps, xn,
-                     reinterpret_cast<float*>(sv + L.inv_sd));
-  HCK(hipGetLastError());
+  HCK(input_norm(in, B, in_eps, xn, reinterpret_cast<float*>(sv + L.inv_sd), st));
   for (int l = 0; l < 7; ++l) {
-    const HnTrainLayer& S = kHardnetTrainLayers[l];
-    const long ho = hout_of(S), hw = ho * ho;
-    // this layer's input: the normalised patch, or relu(z) of the previous layer (x the dropout
-    // mask before conv6, HardNet.py:299)
     const ActIn a{l == 0 ? xn : reinterpret_cast<const float*>(sv + L.z[l - 1]), l > 0 ? 1 : 0,
                   l == 6 ? drop_p : 0.f, seed};
     float* z = reinterpret_cast<float*>(sv + L.z[l]);
-    const int tf = hn_knobs().train_f32;
-    if (l == 0 && !(tf & 64)) {  // conv0: k_fwd0 (taps as the MFMA's K)
-      hipLaunchKernelGGL(k_fwd0, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, xn, W[0], B, z);
-      HCK(hipGetLastError());
-    } else if (l >= 1 && l <= 5 && !(tf & 1))  // conv1..5: the bf16x3 MFMA conv kernels
-      HCK(conv_bf16x3(l, false, a.z, true, B, W[l], z, sc, L, st));
-    else if ((l == 1 || l == 3 || l == 5) && !(tf & 8)) {  // stride-1 3x3: k_fwd3 (f32 MFMA)
-      if (l == 1) HCK((fwd3<32, 32, 32>(a.z, true, W[l], B, z, st)));
-      const bool sh = !(tf & 128);  // conv3 / conv5: the shared-ring form
-      if (l == 3) HCK((sh ? fwd3s<64, 64, 16> : fwd3<64, 64, 16>)(a.z, true, W[l], B, z, st));
-      if (l == 5) HCK((sh ? fwd3s<128, 128, 8> : fwd3<128, 128, 8>)(a.z, true, W[l], B, z, st));
-    } else if ((l == 2 || l == 4) && !(tf & 32)) {  // stride-2 3x3: k_fwd2 (f32 MFMA)
-      // conv2: one ring per wave (shared by 2 waves measured 0.64 vs 0.31 ms); conv4: one ring per two
-      // waves (one per wave needs 128 prefetch registers per lane and spills)
-      if (l == 2) HCK((fwd2<32, 64, 32>(a.z, true, W[l], B, z, st, (tf & 128) != 0)));
-      if (l == 4) HCK((fwd2<64, 128, 16, 2>(a.z, true, W[l], B, z, st, !(tf & 128))));
-    } else
-      HCK(conv_fwd_l(l, a, B, W[l], S.cout, z, reinterpret_cast<float*>(sc + L.part), st));  // Y = W . im2col(a)
-    {
-      const int NS = bn_slices(S.cout, B * hw);
-      double* part = reinterpret_cast<double*>(sc + L.bnpart);
-      float* rstd = reinterpret_cast<float*>(sv + L.rstd[l]);
-      hipLaunchKernelGGL(k_bn_part, dim3(S.cout, NS), dim3(256), 0, st, z, B * hw, NS, part);
-      hipLaunchKernelGGL(k_bn_apply, bn_row_grid(S.cout, B * hw), dim3(256), 0, st, z, B * hw, part, NS, bn_eps, mom,
-                         rmean ? rmean[l] : nullptr, rvar ? rvar[l] : nullptr, rstd);
-      HCK(hipGetLastError());
-    }
+    HCK(conv_fwd(l, tf, 0, a, W[l], B, z, sc, L, st));
+    HCK(bn_fwd(l, z, B, rmean ? rmean[l] : nullptr, rvar ? rvar[l] : nullptr, mom, bn_eps,
+               reinterpret_cast<float*>(sv + L.rstd[l]), sc, L, st));
   }
-  hipLaunchKernelGGL(k_l2_fwd, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st,
-                     reinterpret_cast<const float*>(sv + L.z[6]), B, l2_eps, out);
-  return hipGetLastError();
+  return l2_fwd(reinterpret_cast<const float*>(sv + L.z[6]), B, l2_eps, out, st);
 }
 
 hipError_t hn_train_backward(const float* dout, long B, const float* const* W, float* const* dW, float* din,
                              float l2_eps, float drop_p, unsigned long long seed, char* sv, char* sc, hipStream_t st) {
   const HnTrainWs L = hn_train_layout(B);
+  const int tf = hn_knobs().train_f32;
   HCK(hipMemsetAsync(sc + L.zero, 0, 128 * sizeof(float), st));
   const float* xn = reinterpret_cast<const float*>(sv + L.xn);
   float* gbuf[2] = {reinterpret_cast<float*>(sc + L.g0), reinterpret_cast<float*>(sc + L.g1)};
-  // g: gradient w.r.t. layer l's output activation a_l (a_6 = z_6 into the L2 norm; a_5 =
-  // dropout(relu(z_5)); a_l = relu(z_l) below), then in place w.r.t. its conv output
   float* g = gbuf[0];
-  hipLaunchKernelGGL(k_l2_bwd, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st,
-                     reinterpret_cast<const float*>(sv + L.z[6]), dout, B, l2_eps, g);
-  HCK(hipGetLastError());
+  HCK(l2_bwd(reinterpret_cast<const float*>(sv + L.z[6]), dout, B, l2_eps, g, st));
   for (int l = 6; l >= 0; --l) {
-    const HnTrainLayer& S = kHardnetTrainLayers[l];
-    const long ho = hout_of(S), hw = ho * ho, K = (long)S.cin * S.ks * S.ks;
-    {
-      const int NS = bn_slices(S.cout, B * hw);
-      double* part = reinterpret_cast<double*>(sc + L.bnpart);
-      const float* zl = reinterpret_cast<const float*>(sv + L.z[l]);
-      hipLaunchKernelGGL(k_bn_bwd_part, dim3(S.cout, NS), dim3(256), 0, st, g, zl, B * hw, NS, l < 6 ? 1 : 0,
-                         l == 5 ? drop_p : 0.f, seed, part);
-      hipLaunchKernelGGL(k_bn_bwd_apply, bn_row_grid(S.cout, B * hw), dim3(256), 0, st, g, zl, B * hw, part, NS,
-                         reinterpret_cast<const float*>(sv + L.rstd[l]), l < 6 ? 1 : 0, l == 5 ? drop_p : 0.f, seed);
-      HCK(hipGetLastError());
-    }
+    HCK(bn_bwd(l, g, reinterpret_cast<const float*>(sv + L.z[l]), reinterpret_cast<const float*>(sv + L.rstd[l]), B,
+               drop_p, seed, sc, L, st));
     const ActIn a{l == 0 ? xn : reinterpret_cast<const float*>(sv + L.z[l - 1]), l > 0 ? 1 : 0,
                   l == 6 ? drop_p : 0.f, seed};
     float* gin = gbuf[(7 - l) & 1];  // gradient w.r.t. this layer's input activation
-    const bool want_in = l > 0 || din;
-    // dW [Cout][K] = dY [Cout][B hw] . im2col(a)^T (split-K slices summed in fp64)
-    float* part = reinterpret_cast<float*>(sc + L.part);
-    if (l == 0 && !(hn_knobs().train_f32 & 64)) {  // conv0: k_wgrad0 (taps as the MFMA's N)
-      const long ns = wgrad0_slices(B);
-      hipLaunchKernelGGL(k_wgrad0, dim3((unsigned)(ns / 4)), dim3(256), 0, st, xn, g, B, part);
-      HCK(hipGetLastError());
-      GemmArgs gs{nullptr, nullptr, dW[0], 32, 9, 0, 0, 0, 0, 0, 9, 1, 1.f, 0.f};
-      hipLaunchKernelGGL(k_splitk_sum, dim3((unsigned)((32 * 9 + 63) / 64)), dim3(1024), 0, st, gs, (int)ns, part);
-      HCK(hipGetLastError());
-    } else if ((l == 1 || l == 3 || l == 5) && !(hn_knobs().train_f32 & 4)) {  // stride-1 3x3: k_wgrad3
-      const float* zx = reinterpret_cast<const float*>(sv + L.z[l - 1]);
-      if (l == 1) HCK((wgrad3<32, 32, 32>(zx, g, B, dW[l], part, st)));
-      if (l == 3) HCK((wgrad3<64, 64, 16>(zx, g, B, dW[l], part, st)));
-      if (l == 5) HCK((wgrad3<128, 128, 8>(zx, g, B, dW[l], part, st)));
-    } else if ((l == 2 || l == 4) && !(hn_knobs().train_f32 & 32)) {  // stride-2 3x3: k_wgrad2
-      const float* zx = reinterpret_cast<const float*>(sv + L.z[l - 1]);
-      if (l == 2) HCK((wgrad2<32, 64, 16>(zx, g, B, dW[l], part, st)));
-      if (l == 4) HCK((wgrad2<64, 128, 8>(zx, g, B, dW[l], part, st)));
-    } else {
-      HCK(conv_wgrad_l(l, a, B, g, S.cout, dW[l], part, st));
-    }
-    if (want_in && S.s == 1 && S.ks == 3 && l >= 1 && !(hn_knobs().train_f32 & 16)) {
-      // stride-1 3x3 (Cin = Cout): the data gradient is k_fwd3 over dY with the flipped weights
-      float* wf = reinterpret_cast<float*>(sc + L.wt);
-      hipLaunchKernelGGL(k_wflip, dim3((unsigned)((S.cout * S.cin * 9 + 255) / 256)), dim3(256), 0, st, W[l], S.cout,
-                         S.cin, wf);
-      HCK(hipGetLastError());
-      if (l == 1) HCK((fwd3<32, 32, 32>(g, false, wf, B, gin, st)));
-      const bool sh = !(hn_knobs().train_f32 & 128);
-      if (l == 3) HCK((sh ? fwd3s<64, 64, 16> : fwd3<64, 64, 16>)(g, false, wf, B, gin, st));
-      if (l == 5) HCK((sh ? fwd3s<128, 128, 8> : fwd3<128, 128, 8>)(g, false, wf, B, gin, st));
-    } else if (want_in && S.s == 1 && S.ks == 3 && l >= 1 && !(hn_knobs().train_f32 & 2)) {
-      // stride-1 3x3 (conv1 / conv3 / conv5: Cin = Cout): the data gradient is the same conv with
-      // the weights flipped and transposed, on the bf16x3 MFMA conv kernels
-      HCK(conv_bf16x3(l, true, g, false, B, W[l], gin, sc, L, st));
-    } else if (want_in && S.s == 1 && S.ks == 3) {
-      // stride-1 3x3: d a_{l-1} [Cin][B H H] = implicit col2im-gather GEMM Wt . dY (every tap lands)
-      HCK(conv_dgrad_l(l, g, B, W[l], S.cout, reinterpret_cast<float*>(sc + L.wt), gin, st));
-    } else if (want_in && (l == 2 || l == 4) && !(hn_knobs().train_f32 & 32)) {
-      // stride-2 3x3: k_dgrad2 (the parity classes' taps only, f32 MFMA)
-      const bool sh = !(hn_knobs().train_f32 & 128);
-      if (l == 2) HCK((dgrad2<64, 32, 16>(g, W[l], B, gin, st, sh)));
-      if (l == 4) HCK((dgrad2<128, 64, 8>(g, W[l], B, gin, st, sh)));
-    } else if (want_in) {
-      // stride 2 (3 of 4 taps miss a given input pixel) and the 8x8 conv6 (one tap per pixel):
-      // dcol [K][n hw] = W^T [K][Cout] . dY, then the gather col2im, in chunks of patches
-      float* col = reinterpret_cast<float*>(sc + L.col);
-      const long nc = chunk_of(S, B);
-      for (long n0 = 0; n0 < B; n0 += nc) {
-        const long n = std::min(nc, B - n0);
-        GemmArgs gd{W[l], g + n0 * hw, col, K, n * hw, S.cout, 1, K, B * hw, 1, n * hw, 1, 1.f, 0.f};
-        HCK(gemm(gd, st));
-        if (S.ks == 8 && ho == 1)  // conv6: the column matrix is the gradient, transposed
-          hipLaunchKernelGGL(k_col6_to_cnhw, dim3(S.cin, (unsigned)((n + 63) / 64)), dim3(256), 0, st, col, B, n0,
-                             n, gin);
-        else
-          hipLaunchKernelGGL(k_col2im, dim3(grid_for((long)S.cin * n * S.hin * S.hin)), dim3(256), 0, st, col,
-                             S.cin, B, S.hin, S.hin, S.ks, S.s, S.pad, (int)ho, (int)ho, n0, n, gin);
-        HCK(hipGetLastError());
-      }
-    }
+    HCK(conv_wgrad(l, tf, 0, a, g, B, dW[l], sc, L, st));
+    if (l > 0 || din) HCK(conv_dgrad(l, tf, 0, 0, g, W[l], B, gin, sc, L, st));
     g = gin;
   }
-  if (din) {
-    // input_norm with detached mean / std (HardNet.py:309-310): d input = d xn / (std + eps)
-    hipLaunchKernelGGL(k_scale_rows, dim3(grid_for(B * 1024)), dim3(256), 0, st, g, B,
-                       reinterpret_cast<const float*>(sv + L.inv_sd));
-    HCK(hipGetLastError());
-    HCK(hipMemcpyAsync(din, g, (size_t)B * 1024 * 4, hipMemcpyDeviceToDevice, st));
-  }
+  if (din) HCK(input_norm_bwd(g, reinterpret_cast<const float*>(sv + L.inv_sd), B, din, st));
   return hipSuccess;
 }
+
+// one layer operation on caller-owned buffers (hn_hardnet_train_layer_op; the argument roles are the header's)
+hipError_t hn_train_layer_op(const HnTrainOpArgs& o, char* sc, hipStream_t st) {
+  const int tf = o.tf < 0 ? hn_knobs().train_f32 : o.tf, l = o.layer;
+  const long B = o.B;
+  const HnTrainWs L = hn_train_layout(B, tf, o.ns);
+  HCK(hipMemsetAsync(sc + L.zero, 0, 128 * sizeof(float), st));
+  const ActIn a{o.x, l > 0 ? 1 : 0, l == 6 ? o.drop_p : 0.f, o.seed};
+  switch (o.op) {
+    case HN_TRAIN_OP_INPUT_NORM: return input_norm(o.x, B, o.in_eps, o.y, o.aux0, st);
+    case HN_TRAIN_OP_CONV_FWD: return conv_fwd(l, tf, o.ns, a, o.w, B, o.y, sc, L, st);
+    case HN_TRAIN_OP_BN_FWD: return bn_fwd(l, o.y, B, o.aux1, o.aux2, o.mom, o.bn_eps, o.aux0, sc, L, st);
+    case HN_TRAIN_OP_L2_FWD: return l2_fwd(o.x, B, o.l2_eps, o.y, st);
+    case HN_TRAIN_OP_L2_BWD: return l2_bwd(o.x, o.w, B, o.l2_eps, o.y, st);
+    case HN_TRAIN_OP_BN_BWD: return bn_bwd(l, o.y, o.x, o.w, B, o.drop_p, o.seed, sc, L, st);
+    case HN_TRAIN_OP_CONV_WGRAD: return conv_wgrad(l, tf, o.ns, a, o.w, B, o.y, sc, L, st);
+    case HN_TRAIN_OP_CONV_DGRAD: return conv_dgrad(l, tf, o.ns, o.chunk, o.x, o.w, B, o.y, sc, L, st);
+    case HN_TRAIN_OP_INPUT_NORM_BWD: return input_norm_bwd(o.y, o.x, B, o.aux0, st);
+  }
+  return hipErrorInvalidValue;
+}
+

@@ -524,6 +524,49 @@ int hn_hardnet_train_backward(const float* d_dout, int64_t batch, const float* c
                               void* d_saved, size_t saved_bytes, void* d_scratch, size_t scratch_bytes,
                               void* hip_stream);
 
+/* Test and diagnostic entry, NO STABILITY PROMISE (an addition: HN_ABI_VERSION stays 2, but the argument list may
+ * change with any release): one layer operation of the train step above, alone, on caller-owned buffers.  The step
+ * functions are loops over the same code, so what this entry runs is what they run.
+ *   layer          0..6 (read by the CONV_* and BN_* operations only, but always checked).
+ *   train_f32_bits the HN_TRAIN_F32 bits (0..255) that choose a convolution's kernel form; -1: the process's.
+ *   row_segments   0: by batch, as the step; 1, 2 or 4: the row segments per patch of the ring kernels (clamped to
+ *                  what the kernel's geometry allows).  Non-zero only where the chosen form has row segments.
+ *   dgrad_chunk    0: as the step; n: patches per column chunk (1..batch) of the column-GEMM data gradient.
+ *                  Non-zero only for CONV_DGRAD where the chosen form is the column GEMM.
+ * Activations are CNHW ([C][batch][H][W], fp32), all device pointers 16-byte aligned:
+ *   op              d_x                     d_w              d_y                    d_aux0 / 1 / 2
+ *   INPUT_NORM      in [B][1024]            -                xn [B][1024]           1/(std+eps) [B] / - / -
+ *   CONV_FWD        input of layer l (*)    W[l]             conv output            -
+ *   BN_FWD          -                       -                conv output, in place  rstd [Cout] out / running_mean /
+ *                                                                                   running_var (both or neither)
+ *   L2_FWD          z6 [128][B]             -                out [B][128]           -
+ *   L2_BWD          z6 [128][B]             dout [B][128]    dz6 [128][B]           -
+ *   BN_BWD          z_l (BN output)         rstd [Cout]      gradient, in place     -
+ *   CONV_WGRAD      input of layer l (*)    dY               dW[l]                  -
+ *   CONV_DGRAD      dY                      W[l]             d input activation     -
+ *   INPUT_NORM_BWD  1/(std+eps) [B]         -                d xn, scaled in place  d_in [B][1024] (a copy) / - / -
+ * (*) layer 0: the normalised patch; else the previous layer's BN output z, pre-activation: the kernel applies the
+ * ReLU (and, for layer 6, the dropout of dropout_p / seed) as the step does.  BN_BWD masks with ReLU for layers 0..5
+ * and with the dropout for layer 5.  d_scratch: hn_hardnet_train_layer_op_workspace_bytes of the same batch, bits and
+ * row_segments. */
+enum hn_train_op {
+  HN_TRAIN_OP_INPUT_NORM = 0,
+  HN_TRAIN_OP_CONV_FWD = 1,
+  HN_TRAIN_OP_BN_FWD = 2,
+  HN_TRAIN_OP_L2_FWD = 3,
+  HN_TRAIN_OP_L2_BWD = 4,
+  HN_TRAIN_OP_BN_BWD = 5,
+  HN_TRAIN_OP_CONV_WGRAD = 6,
+  HN_TRAIN_OP_CONV_DGRAD = 7,
+  HN_TRAIN_OP_INPUT_NORM_BWD = 8
+};
+int hn_hardnet_train_layer_op_workspace_bytes(int32_t train_f32_bits, int32_t row_segments, int64_t batch,
+                                              size_t* scratch_bytes_out);
+int hn_hardnet_train_layer_op(int32_t op, int32_t layer, int32_t train_f32_bits, int32_t row_segments,
+                              int64_t dgrad_chunk, int64_t batch, const float* d_x, const float* d_w, float* d_y,
+                              float* d_aux0, float* d_aux1, float* d_aux2, float momentum, float dropout_p,
+                              uint64_t seed, void* d_scratch, size_t scratch_bytes, void* hip_stream);
+
 /* Train-mode hardnetNAS (second half; hardnetNAS/supernet_functions/
  * training_functions_supernet.py:88-103 runs the module in train() through autograd):
  *   desc->kind HN_KIND_NAS           the sampled descriptor (op[i] per layer), model_supernet.py:53-85

@@ -7,7 +7,8 @@ over those files:
     HN_LIB=<library built from that commit> python tests/abi_error_cases.py --record
 
 so it pins every message, every code and, through the cases that break two rules at once (tags with "+"), the order
-of the checks inside an entry point.
+of the checks inside an entry point.  An entry point added since (hn_hardnet_train_layer_op and its size query) is
+recorded from the library that adds it; the rows of the older ones must come out unchanged.
 
 A case ends in HN_ERR_ARG (1), HN_ERR_WORKSPACE (4) or one of the documented early HN_OK returns (n == 0,
 n_images == 0, hn_warp_score without outputs); none reaches a launch.  Device pointers are the placeholder 4096,
@@ -117,6 +118,12 @@ SPEC = {
                                  ("momentum", 0.1), ("dropout_p", 0.1), ("seed", 1), ("out", P)] + _SV + [("st", None)],
     "hn_hardnet_train_backward": [("dout", P), ("batch", 4), ("weights", T7), ("dweights", T7), ("din", P),
                                   ("dropout_p", 0.1), ("seed", 1)] + _SV + [("st", None)],
+    "hn_hardnet_train_layer_op_workspace_bytes": [("bits", 17), ("row_segments", 0), ("batch", 4), ("out", size)],
+    # conv_dgrad of layer 4 under bits 32 + 17: the column-GEMM form, so dgrad_chunk may be given
+    "hn_hardnet_train_layer_op": [("op", 7), ("layer", 4), ("bits", 49), ("row_segments", 0), ("dgrad_chunk", 2),
+                                  ("batch", 4), ("x", P), ("w", P), ("y", P), ("aux0", None), ("aux1", None),
+                                  ("aux2", None), ("momentum", 0.1), ("dropout_p", 0.1), ("seed", 1), ("scratch", P),
+                                  ("scratch_bytes", BIG), ("st", None)],
     "hn_nas_train_tensor_count": [("desc", DESC), ("n_out", size)],
     "hn_nas_train_workspace_bytes": [("desc", DESC), ("batch", 4), ("saved_out", size), ("scratch_out", size)],
     "hn_nas_train_forward": [("desc", DESC), ("in", P), ("batch", 4), ("tensors", nas_tensors()), ("momentum", 0.1),
@@ -260,6 +267,37 @@ def _cases():
             ("dweights NULL", {"dweights": None}),
         ("dweights hole", {"dweights": table(7, 2)}), ("dropout_p", {"dropout_p": -0.1}),
         ("dout NULL+dweights NULL", {"dout": None, "dweights": None}),
+    ])
+    add("hn_hardnet_train_layer_op_workspace_bytes", [
+        ("out NULL", {"out": None}), ("batch<2", {"batch": 1}), ("batch>2^24", {"batch": (1 << 24) + 1}),
+        ("bits", {"bits": 256}), ("bits<-1", {"bits": -2}), ("row_segments", {"row_segments": 3}),
+        ("out NULL+batch<2", {"out": None, "batch": 1}), ("batch<2+bits", {"batch": 1, "bits": 256}),
+        ("bits+row_segments", {"bits": 256, "row_segments": 8})])
+    ring = {"bits": 17, "dgrad_chunk": 0}  # the same operation as k_dgrad2: row segments, no chunks
+    bn_fwd = {"op": 2, "dgrad_chunk": 0, "x": None, "w": None, "aux0": P}
+    add("hn_hardnet_train_layer_op", [
+        ("batch<2", {"batch": 1}), ("bits", {"bits": 256}), ("row_segments", {"row_segments": 3}),
+        ("op", {"op": 9}), ("op<0", {"op": -1}), ("layer", {"layer": 7}), ("layer<0", {"layer": -1}),
+        ("row_segments without a ring", {"row_segments": 2}),
+        ("row_segments on bn_fwd", dict(bn_fwd, row_segments=4)),
+        ("dgrad_chunk<0", {"dgrad_chunk": -1}), ("dgrad_chunk>batch", {"dgrad_chunk": 5}),
+        ("dgrad_chunk on a ring", dict(ring, dgrad_chunk=2)),
+        ("dgrad_chunk on conv_fwd", {"op": 1}),
+        ("x NULL", {"x": None}), ("w NULL", {"w": None}), ("y NULL", {"y": None}),
+        ("bn_fwd aux0 NULL", dict(bn_fwd, aux0=None)),
+        ("bn_fwd rvar alone", dict(bn_fwd, aux2=P)),
+        ("dropout_p", {"dropout_p": 1.0}), ("dropout_p NaN", {"dropout_p": NAN}),
+        ("y misaligned", {"y": P + 8}), ("scratch misaligned", {"scratch": P + 4}),
+        ("scratch NULL", {"scratch": None}), ("scratch small", {"scratch_bytes": 0}),
+        ("batch<2+op", {"batch": 1, "op": 9}), ("row_segments+op", {"row_segments": 3, "op": 9}),
+        ("op+layer", {"op": 9, "layer": 7}), ("layer+row_segments without a ring", {"layer": 7, "row_segments": 2}),
+        ("row_segments without a ring+dgrad_chunk<0", {"row_segments": 2, "dgrad_chunk": -1}),
+        ("dgrad_chunk on a ring+x NULL", dict(ring, dgrad_chunk=2, x=None)),
+        ("x NULL+dropout_p", {"x": None, "dropout_p": 1.0}),
+        ("bn_fwd rmean alone+dropout_p", dict(bn_fwd, aux1=P, dropout_p=-1.0)),
+        ("dropout_p+w misaligned", {"dropout_p": 1.0, "w": P + 4}),
+        ("x misaligned+scratch NULL", {"x": P + 8, "scratch": None}),
+        ("scratch NULL+scratch small", {"scratch": None, "scratch_bytes": 0}),
     ])
     nas_desc_rows = [
         ("desc NULL", {"desc": None}), ("kind", {"desc": desc("hardnet")}), ("n_layers", {"desc": desc(n_layers=0)}),

@@ -56,7 +56,7 @@ def check_prototypes(lib, names):
 
 def test_prototypes_agree_with_the_header():
     decl = declared_prototypes()
-    assert len(decl) == 53 and decl["hn_abi_version"][1] == [] and decl["hn_last_error"][1] == []
+    assert len(decl) == 55 and decl["hn_abi_version"][1] == [] and decl["hn_last_error"][1] == []
     check_prototypes(N.load_library(), N.EXPORTED)
     assert N.EXPORTED == list(N._PROTOTYPES)
     lib = N.load_library()
