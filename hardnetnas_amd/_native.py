@@ -39,6 +39,8 @@ HN_MAX_LAYERS = 8
 ABI_VERSION = 2   # HN_ABI_VERSION
 DET_TRAIN_TENSORS = 40  # HN_DET_TRAIN_TENSORS
 LOSS_TYPES = {"triplet_margin": 0, "softmax": 1, "contrastive": 2}  # enum hn_loss_type
+BATCH_REDUCES = {"min": 0, "average": 1, "random": 2}  # enum hn_batch_reduce (hardnet_mi355x_loss_reduce.h)
+AVERAGE_MAX_BATCH = 65536  # hn_hardnet_loss_reduce_*: the cap of HN_REDUCE_AVERAGE
 MATCH_METRICS = {"unit": 0, "l2": 1}  # enum hn_metric
 RESIZE_MODES = {"none": 0, "cv2": 1, "pil": 2}  # enum hn_resize
 
@@ -135,6 +137,14 @@ _PROTOTYPES = {
 # every function returns int (ctypes' default restype) but these
 _RESTYPES = {"hn_det_destroy": None, "hn_destroy": None, "hn_last_error": ctypes.c_char_p}
 EXPORTED = list(_PROTOTYPES)
+# the extension header include/hardnet_mi355x_loss_reduce.h: loss_HardNet's 'average' and 'random' reductions
+# (tests/test_loss_reduce_abi.py compares this table with that header)
+_LOSS_REDUCE_PROTOTYPES = {
+    "hn_hardnet_loss_reduce_workspace_bytes": (I32, I64, SP),
+    "hn_hardnet_loss_reduce_forward": (P, P, P, I64, I32, I32, I32, F32, I32, P, P, S, P),
+    "hn_hardnet_loss_reduce_backward": (P, P, P, I64, I32, I32, I32, F32, I32, P, P, P, P, S, P),
+}
+EXPORTED_LOSS_REDUCE = list(_LOSS_REDUCE_PROTOTYPES)
 
 
 def lib_path() -> str:
@@ -154,7 +164,7 @@ def load_library():
                 f"hardnetnas_amd native library not found at {path}; build it with "
                 "`python -c 'import __graft_entry__ as g; g.build()'` (make -C hardnetnas_amd/csrc)")
         lib = ctypes.CDLL(path)
-        for name, argtypes in _PROTOTYPES.items():
+        for name, argtypes in list(_PROTOTYPES.items()) + list(_LOSS_REDUCE_PROTOTYPES.items()):
             fn = getattr(lib, name)
             fn.argtypes = list(argtypes)
             if name in _RESTYPES:
@@ -465,6 +475,46 @@ class HardNetLossFunction(torch.autograd.Function):
         _call(a.device, "hn_hardnet_loss_backward", a, p, a.shape[0], a.shape[1], int(swap), margin, lt, dl, ga, gp,
               *_buf(saved))
         return ga, gp, None, None, None
+
+
+class HardNetLossReduceFunction(torch.autograd.Function):
+    """loss_HardNet with batch_reduce 'average' or 'random' (hardnet/Losses.py:124-138) and its backward on the
+    kernels of hn_loss_dense.hip / hn_loss.hip: no B x B matrix, bit-identical call to call.
+    ``apply(anchor, positive, idx, reduce, anchor_swap, margin, loss_type)``: anchor / positive [B,128] fp32 HIP
+    tensors; ``idx`` the [B] int64 negatives of 'random' (any values: the kernel clamps each to [0, B-1]), None for
+    'average'."""
+
+    @staticmethod
+    def forward(ctx, anchor, positive, idx, reduce, anchor_swap, margin, loss_type):
+        if reduce not in ("average", "random"):
+            raise ValueError(f"HardNetLossReduceFunction runs 'average' and 'random', not {reduce!r}")
+        a, p = _aligned16(anchor), _aligned16(positive)
+        b = a.shape[0]
+        if reduce == "random":
+            if idx is None or idx.numel() != b:
+                raise ValueError("'random' needs one index per row")
+            idx = idx.detach().to(device=a.device, dtype=torch.int64).contiguous().reshape(b)
+        else:
+            idx = None
+        kind = BATCH_REDUCES[reduce]
+        saved = torch.empty(_size("hn_hardnet_loss_reduce_workspace_bytes", kind, b), device=a.device,
+                            dtype=torch.uint8)
+        loss = torch.empty((), device=a.device, dtype=torch.float32)
+        ctx.args = (kind, int(bool(anchor_swap)), float(margin), LOSS_TYPES[loss_type])
+        _call(a.device, "hn_hardnet_loss_reduce_forward", a, p, idx, b, a.shape[1], *ctx.args, loss, *_buf(saved))
+        ctx.idx = idx
+        ctx.save_for_backward(a, p, saved)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable  # the fused backward records no graph (no double backward)
+    def backward(ctx, dloss):
+        a, p, saved = ctx.saved_tensors
+        ga, gp = torch.empty_like(a), torch.empty_like(p)
+        dl = dloss.detach().to(device=a.device, dtype=torch.float32).contiguous().reshape(1)
+        _call(a.device, "hn_hardnet_loss_reduce_backward", a, p, ctx.idx, a.shape[0], a.shape[1], *ctx.args, dl, ga,
+              gp, *_buf(saved))
+        return ga, gp, None, None, None, None, None
 
 
 def hardnet_loss_saved_argmins(saved: torch.Tensor, b: int):

@@ -253,6 +253,79 @@ extern "C" int hn_hardnet_loss_backward(const float* d_anchor, const float* d_po
   return HN_OK;
 }
 
+// loss_HardNet's 'average' and 'random' reductions (hn_loss_dense.hip, hn_loss.hip)
+static constexpr int64_t kAverageMaxBatch = 65536;  // B^2 work beyond it would occupy the GPU for seconds per call
+static int reduce_kind(int32_t batch_reduce) {
+  if (batch_reduce == HN_REDUCE_MIN)
+    return fail(HN_ERR_ARG, "HN_REDUCE_MIN runs on hn_hardnet_loss_train_forward / hn_hardnet_loss_backward");
+  if (batch_reduce != HN_REDUCE_AVERAGE && batch_reduce != HN_REDUCE_RANDOM)
+    return fail(HN_ERR_ARG, "unknown batch_reduce " + std::to_string(batch_reduce));
+  return HN_OK;
+}
+static size_t average_saved_bytes(long b) { return b <= kAverageMaxBatch ? hn_loss_dense_saved_bytes(b) : 0; }
+
+extern "C" int hn_hardnet_loss_reduce_workspace_bytes(int32_t batch_reduce, int64_t batch, size_t* bytes_out) {
+  if (int rc = reduce_kind(batch_reduce)) return rc;
+  const int64_t cap = batch_reduce == HN_REDUCE_AVERAGE ? kAverageMaxBatch : (int64_t)1 << 22;
+  if (!bytes_out || batch < 1 || batch > cap)
+    return fail(HN_ERR_ARG, "batch out of range (1 .. " + std::to_string(cap) + " for this batch_reduce)");
+  *bytes_out = batch_reduce == HN_REDUCE_AVERAGE ? hn_loss_dense_saved_bytes((long)batch)
+                                                 : hn_loss_train_saved_bytes((long)batch);
+  return HN_OK;
+}
+
+static int loss_reduce_args(const float* a, const float* p, const int64_t* idx, int64_t batch, int32_t dim,
+                            int32_t batch_reduce, int32_t loss_type, void* saved, size_t saved_bytes) {
+  if (int rc = reduce_kind(batch_reduce)) return rc;
+  if (batch_reduce == HN_REDUCE_AVERAGE && batch > kAverageMaxBatch)
+    return fail(HN_ERR_ARG, "batch out of range (1 .. " + std::to_string(kAverageMaxBatch) + " for HN_REDUCE_AVERAGE)");
+  if (int rc = loss_args(a, p, batch, dim, loss_type, saved, saved_bytes,
+                         batch_reduce == HN_REDUCE_AVERAGE ? average_saved_bytes : hn_loss_train_saved_bytes))
+    return rc;
+  if (batch_reduce == HN_REDUCE_RANDOM) {
+    if (!idx) return fail(HN_ERR_ARG, "HN_REDUCE_RANDOM needs d_idx");
+    if (hn_misaligned(8, idx)) return fail(HN_ERR_ARG, "d_idx must be 8-byte aligned");
+  }
+  return HN_OK;
+}
+
+extern "C" int hn_hardnet_loss_reduce_forward(const float* d_anchor, const float* d_positive, const int64_t* d_idx,
+                                              int64_t batch, int32_t dim, int32_t batch_reduce, int32_t anchor_swap,
+                                              float margin, int32_t loss_type, float* d_loss, void* d_saved,
+                                              size_t saved_bytes, void* hip_stream) {
+  if (int rc = loss_reduce_args(d_anchor, d_positive, d_idx, batch, dim, batch_reduce, loss_type, d_saved, saved_bytes))
+    return rc;
+  if (!d_loss) return fail(HN_ERR_ARG, "NULL device pointer");
+  const hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  if (batch_reduce == HN_REDUCE_AVERAGE)
+    HIPCHK(hn_launch_loss_dense_fwd(d_anchor, d_positive, (int)batch, anchor_swap ? 1 : 0, margin, loss_type, d_loss,
+                                    d_saved, st));
+  else
+    HIPCHK(hn_launch_loss_random_fwd(d_anchor, d_positive, reinterpret_cast<const long long*>(d_idx), (int)batch,
+                                     anchor_swap ? 1 : 0, margin, loss_type, d_loss, d_saved, st));
+  return HN_OK;
+}
+
+extern "C" int hn_hardnet_loss_reduce_backward(const float* d_anchor, const float* d_positive, const int64_t* d_idx,
+                                               int64_t batch, int32_t dim, int32_t batch_reduce, int32_t anchor_swap,
+                                               float margin, int32_t loss_type, const float* d_dloss,
+                                               float* d_grad_anchor, float* d_grad_positive, void* d_saved,
+                                               size_t saved_bytes, void* hip_stream) {
+  if (int rc = loss_reduce_args(d_anchor, d_positive, d_idx, batch, dim, batch_reduce, loss_type, d_saved, saved_bytes))
+    return rc;
+  if (!d_dloss || !d_grad_anchor || !d_grad_positive) return fail(HN_ERR_ARG, "NULL device pointer");
+  if (hn_misaligned(8, d_grad_anchor, d_grad_positive))
+    return fail(HN_ERR_ARG, "gradient pointers must be 8-byte aligned");
+  const hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  if (batch_reduce == HN_REDUCE_AVERAGE)
+    HIPCHK(hn_launch_loss_dense_bwd(d_anchor, d_positive, (int)batch, anchor_swap ? 1 : 0, margin, loss_type, d_dloss,
+                                    d_grad_anchor, d_grad_positive, d_saved, st));
+  else  // the selections lie in d_saved: the 'min' backward runs on them as it is
+    HIPCHK(hn_launch_loss_train_bwd(d_anchor, d_positive, (int)batch, anchor_swap ? 1 : 0, margin, loss_type, d_dloss,
+                                    d_grad_anchor, d_grad_positive, d_saved, st));
+  return HN_OK;
+}
+
 extern "C" int hn_neimask_loss_workspace_bytes(int64_t batch, size_t* bytes_out) {
   if (!bytes_out || batch < 1 || batch > (1 << 22)) return fail(HN_ERR_ARG, "batch out of range");
   *bytes_out = hn_neimask_saved_bytes((long)batch);

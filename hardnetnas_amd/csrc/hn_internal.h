@@ -441,6 +441,18 @@ hipError_t hn_launch_loss_train_fwd(const float* a, const float* p, int B, int s
 hipError_t hn_launch_loss_train_bwd(const float* a, const float* p, int B, int swap, float margin, int type,
                                     const float* dloss, float* ga, float* gp, void* saved, hipStream_t st);
 
+// batch_reduce 'random' (hn_loss.hip): tidx [B] int64, each value clamped to [0, B-1] on load; the saved layout and
+// the backward are 'min''s (hn_loss_train_saved_bytes, hn_launch_loss_train_bwd)
+hipError_t hn_launch_loss_random_fwd(const float* a, const float* p, const long long* tidx, int B, int swap,
+                                     float margin, int type, float* loss, void* saved, hipStream_t st);
+
+// batch_reduce 'average' and its backward on the f32-input MFMA (hn_loss_dense.hip)
+size_t hn_loss_dense_saved_bytes(long B);
+hipError_t hn_launch_loss_dense_fwd(const float* a, const float* p, int B, int swap, float margin, int type,
+                                    float* loss, void* saved, hipStream_t st);
+hipError_t hn_launch_loss_dense_bwd(const float* a, const float* p, int B, int swap, float margin, int type,
+                                    const float* dloss, float* ga, float* gp, void* saved, hipStream_t st);
+
 // FDLNet's neighbour-mask loss and its backward (hn_neimask.hip); akp / pkp: [B,4] int64 rows (b, y, x, 0)
 size_t hn_neimask_saved_bytes(long B);
 hipError_t hn_launch_neimask_fwd(const float* a, const float* p, const long long* akp, const long long* pkp, int B,

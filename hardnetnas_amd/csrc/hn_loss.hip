@@ -25,6 +25,7 @@
 #include "hn_common.h"
 #include "hn_internal.h"
 #include "hn_loss_gather.h"
+#include "hn_loss_terms.h"
 
 namespace {
 
@@ -32,33 +33,6 @@ constexpr int D = LT_D, TM = LT_TM, TN = LT_TN;
 
 __global__ __launch_bounds__(256) void k_lmin_init(unsigned long long* __restrict__ colbest, int B) {
   for (int i = blockIdx.x * 256 + threadIdx.x; i < B; i += gridDim.x * 256) colbest[i] = ~0ull;
-}
-
-// |v|^2 of every row (a then p), one wave per row; for w < B also the positive distance d_ii from
-// |a_i - p_i|^2 directly: the expanded |a|^2 + |p|^2 - 2 a.p of the distance matrix cancels for the
-// close pairs of a training batch (the reference's fp32 loss carries that error: 2e-6 on a mean of
-// distances), the difference form keeps d_ii at fp32 accuracy
-HN_DEV float diff_sq(const float* a, const float* p, int lane) {
-  const float2 u = reinterpret_cast<const float2*>(a)[lane], v = reinterpret_cast<const float2*>(p)[lane];
-  const float dx = u.x - v.x, dy = u.y - v.y;
-  return wave_sum(fmaf(dx, dx, dy * dy));
-}
-__global__ __launch_bounds__(256) void k_lmin_sq(const float* __restrict__ a, const float* __restrict__ p, int B,
-                                                 float* __restrict__ sq, float* __restrict__ pos,
-                                                 float* __restrict__ posx) {
-  const int w = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (w >= 2 * B) return;
-  const float* r = (w < B ? a + (size_t)w * D : p + (size_t)(w - B) * D);
-  const float2 v = reinterpret_cast<const float2*>(r)[lane];
-  const float s = wave_sum(v.x * v.x + v.y * v.y);
-  if (lane == 0) sq[w] = s;
-  if (w < B) {
-    const float x = diff_sq(a + (size_t)w * D, p + (size_t)w * D, lane);
-    if (lane == 0) {
-      pos[w] = sqrtf(x + 1e-6f) + 1e-8f;
-      posx[w] = x;  // (kept for the backward's sqrt derivative)
-    }
-  }
 }
 
 // One workgroup per 64 anchors, all positives in 64-column tiles.  Thread (ty, tx) computes the
@@ -130,27 +104,6 @@ __global__ __launch_bounds__(256) void k_lmin_tiles(const float* __restrict__ a,
   }
 }
 
-// per-row loss f(pos, mn) and its partials d f / d pos, d f / d mn (autograd's forms)
-HN_DEV float loss_of(int type, float margin, float ps, float mn, float* dpos, float* dmn) {
-  if (type == 0) {  // clamp(margin + pos - mn, min=0); clamp's backward passes at t >= 0
-    const float t = margin + ps - mn;
-    *dpos = t >= 0.f ? 1.f : 0.f;
-    *dmn = -*dpos;
-    return fmaxf(t, 0.f);
-  }
-  if (type == 1) {  // -log(exp_pos / (exp_pos + exp(2 - mn) + eps))
-    const float ep = expf(2.0f - ps), en = expf(2.0f - mn);
-    const float den = ep + en + 1e-8f;
-    *dpos = (en + 1e-8f) / den;
-    *dmn = -en / den;
-    return -logf(ep / den);
-  }
-  const float t = margin - mn;  // clamp(margin - mn, min=0) + pos
-  *dpos = 1.f;
-  *dmn = t >= 0.f ? -1.f : 0.f;
-  return fmaxf(t, 0.f) + ps;
-}
-
 // one workgroup: the mean in a fixed order (deterministic)
 __global__ __launch_bounds__(1024) void k_lmin_finish(const unsigned long long* __restrict__ rowbest,
                                                       const unsigned long long* __restrict__ colbest,
@@ -174,6 +127,27 @@ __global__ __launch_bounds__(1024) void k_lmin_finish(const unsigned long long* 
     double t = 0.0;
     for (int w = 0; w < 16; ++w) t += part[w];
     loss[0] = (float)(t / (double)B);
+  }
+}
+
+// batch_reduce 'random' (Losses.py:131-138): row i's negative is entry (i, t_i), with anchor_swap also entry
+// (t_i, i) -- the 'min' computation with r_i = c_i = t_i, so the two keys go into the rowbest / colbest slots and
+// the finish and the backward run unchanged.  t_i is clamped to [0, B-1] as the first thing done with it: no value
+// of the index list can address memory outside a, p and sq.  One thread per row, the same FMA chain as the tiles.
+__global__ __launch_bounds__(256) void k_lrand_keys(const float* __restrict__ a, const float* __restrict__ p,
+                                                    const float* __restrict__ sq,
+                                                    const long long* __restrict__ tidx, int B, int swap,
+                                                    unsigned long long* __restrict__ rowbest,
+                                                    unsigned long long* __restrict__ colbest) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= B) return;
+  const long long raw = tidx[i];
+  const int t = (int)(raw < 0 ? 0ll : raw > (long long)(B - 1) ? (long long)(B - 1) : raw);
+  const float x = (sq[i] + sq[B + t]) - 2.0f * dot128(a + (size_t)i * D, p + (size_t)t * D);
+  rowbest[i] = key_of(masked_dn(x, t == i), t);
+  if (swap) {
+    const float y = (sq[t] + sq[B + i]) - 2.0f * dot128(a + (size_t)t * D, p + (size_t)i * D);
+    colbest[i] = key_of(masked_dn(y, t == i), t);
   }
 }
 
@@ -290,6 +264,18 @@ hipError_t hn_launch_loss_train_fwd(const float* a, const float* p, int B, int s
   if (swap) hipLaunchKernelGGL(k_lmin_init, dim3(std::min((B + 255) / 256, 1024)), dim3(256), 0, st, s.colbest, B);
   hipLaunchKernelGGL(k_lmin_tiles, dim3((B + TM - 1) / TM), dim3(256), 0, st, a, p, s.sq, B, swap, s.rowbest,
                      s.colbest, s.pos);
+  hipLaunchKernelGGL(k_lmin_finish, dim3(1), dim3(1024), 0, st, s.rowbest, s.colbest, s.pos, B, swap, margin, type,
+                     loss);
+  return hipGetLastError();
+}
+
+// 'random': the same saved layout; its backward is hn_launch_loss_train_bwd
+hipError_t hn_launch_loss_random_fwd(const float* a, const float* p, const long long* tidx, int B, int swap,
+                                     float margin, int type, float* loss, void* saved, hipStream_t st) {
+  const LossSaved s = loss_saved(saved, B);
+  hipLaunchKernelGGL(k_lmin_sq, dim3((2 * B + 3) / 4), dim3(256), 0, st, a, p, B, s.sq, s.pos, s.posx);
+  hipLaunchKernelGGL(k_lrand_keys, dim3((B + 255) / 256), dim3(256), 0, st, a, p, s.sq, tidx, B, swap, s.rowbest,
+                     s.colbest);
   hipLaunchKernelGGL(k_lmin_finish, dim3(1), dim3(1024), 0, st, s.rowbest, s.colbest, s.pos, B, swap, margin, type,
                      loss);
   return hipGetLastError();

@@ -1,10 +1,14 @@
-"""Differentiable ``loss_HardNet`` for training loops (hardnet/Losses.py:87-154, batch_reduce
-'min'), with ``distance_matrix_vector`` (Losses.py:5-13) in the reference's formulation.
+"""Differentiable ``loss_HardNet`` for training loops (hardnet/Losses.py:87-154, batch_reduce 'min',
+'average' and 'random'), with ``distance_matrix_vector`` (Losses.py:5-13) in the reference's formulation.
 
-The training loop calls it as HardNet.py:408-413.  With batch_reduce 'min' on HIP fp32 [B,128]
-descriptors it runs the fused kernels of hn_loss.hip (forward and backward, no B x B matrix); the
-autograd formulation below (the B x B matrix materialised, as in the reference) serves CPU / fp64
-tensors, the 'average' and 'random' reductions and ``fused=False``.  For inference-time mining at
+The training loop calls it as HardNet.py:408-413.  On HIP fp32 [B,128] descriptors every reduction runs on
+HIP kernels, forward and backward, without the B x B matrix: 'min' and 'random' on hn_loss.hip, 'average'
+(B <= 65,536) on the f32-input MFMA kernels of hn_loss_dense.hip.  The autograd formulation below (the B x B
+matrix materialised, as in the reference) serves CPU / fp64 tensors, other widths and ``fused=False``.  The
+other losses HardNet.py:399-419 can call -- ``loss_random_sampling`` with ``distance_vectors_pairwise``,
+``global_orthogonal_regularization``, ``CorrelationPenaltyLoss`` -- are torch formulations (O(B * 128) row
+work with nothing to fuse away).  ``loss_L2Net`` is left out: Losses.py:70 subtracts an int from a bool
+tensor, which current torch refuses, so the reference cannot pin it.  For inference-time mining at
 large B (65,536 pairs) ``hardnetnas_amd._native.pairdist_rows`` / ``hardnet_loss`` and
 ``hardnetnas_amd.distributed.sharded_hardnet_loss`` run the bf16x3 MFMA pair kernel (forward only).
 
@@ -17,7 +21,9 @@ from __future__ import annotations
 
 import torch
 
-__all__ = ["distance_matrix_vector", "loss_HardNet", "SupernetLoss", "loss_neimask", "pair_distance_loss"]
+__all__ = ["distance_matrix_vector", "loss_HardNet", "SupernetLoss", "loss_neimask", "pair_distance_loss",
+           "distance_vectors_pairwise", "loss_random_sampling", "global_orthogonal_regularization",
+           "CorrelationPenaltyLoss"]
 
 
 def distance_matrix_vector(anchor: torch.Tensor, positive: torch.Tensor) -> torch.Tensor:
@@ -32,22 +38,36 @@ def loss_HardNet(anchor: torch.Tensor, positive: torch.Tensor, anchor_swap: bool
                  loss_type: str = "triplet_margin", fused: bool = True) -> torch.Tensor:
     """Hardest-in-batch margin loss (Losses.py:87-154); anchor_ave is accepted and unused, as there.
 
-    batch_reduce 'min' (the training default, HardNet.py:74) on [B,128] fp32 HIP tensors runs the
-    fused kernels (``_native.HardNetLossFunction``: forward and backward without the B x B matrix);
-    ``fused=False``, CPU / fp64 tensors and the other reductions run the reference's autograd
-    formulation here.  'average' (:124-130) takes every masked entry as a negative, paired -- as in
-    the reference -- with the positive distance of its column; 'random' (:131-138) one negative per
-    row at torch.randperm(B) drawn from the CPU generator as the reference draws it."""
+    'average' (:124-130) takes every masked entry as a negative, paired -- as in the reference -- with the
+    positive distance of its column; 'random' (:131-138) one negative per row at torch.randperm(B), drawn once
+    from the CPU generator as the reference draws it, on either path: a seeded run selects the same negatives
+    fused or not.
+
+    Dispatch, with no knob but ``fused``: [B,128] fp32 tensors on one HIP device run the HIP kernels, forward
+    and backward without the B x B matrix -- 'min' (the training default, HardNet.py:74) through
+    ``_native.HardNetLossFunction``, 'average' (B <= 65,536) and 'random' through
+    ``_native.HardNetLossReduceFunction``.  ``fused=False``, CPU / fp64 tensors, other widths and 'average'
+    beyond 65,536 rows run the reference's autograd formulation here."""
     if anchor.size() != positive.size() or anchor.dim() != 2:
         raise ValueError("anchor and positive must be 2-D tensors of the same shape")
     if batch_reduce not in ("min", "average", "random"):
         raise ValueError(f"unknown batch_reduce {batch_reduce!r} (min, average or random)")
     if loss_type not in ("triplet_margin", "softmax", "contrastive"):
         raise ValueError(f"unknown loss_type {loss_type!r}")
-    if (fused and batch_reduce == "min" and anchor.is_cuda and positive.is_cuda
-            and anchor.dtype == torch.float32 and positive.dtype == torch.float32 and anchor.shape[1] == 128):
+    native = (fused and anchor.is_cuda and positive.is_cuda and anchor.dtype == torch.float32
+              and positive.dtype == torch.float32 and anchor.shape[1] == 128)
+    if native and batch_reduce == "min":
         from . import _native
         return _native.HardNetLossFunction.apply(anchor, positive, anchor_swap, margin, loss_type)
+    if native and anchor.device == positive.device and anchor.shape[0] >= 1:
+        from . import _native
+        if batch_reduce == "random":
+            idxs = torch.randperm(anchor.size(0)).long()
+            return _native.HardNetLossReduceFunction.apply(anchor, positive, idxs, "random", anchor_swap, margin,
+                                                           loss_type)
+        if anchor.shape[0] <= _native.AVERAGE_MAX_BATCH:
+            return _native.HardNetLossReduceFunction.apply(anchor, positive, None, "average", anchor_swap, margin,
+                                                           loss_type)
     eps = 1e-8
     d = distance_matrix_vector(anchor, positive) + eps
     b = d.size(1)
@@ -79,6 +99,59 @@ def loss_HardNet(anchor: torch.Tensor, positive: torch.Tensor, anchor_swap: bool
     else:
         loss = torch.clamp(margin - min_neg, min=0.0) + pos
     return loss.mean()
+
+
+def distance_vectors_pairwise(anchor, positive, negative=None):
+    """Row-wise distances sqrt(|x_i|^2 + |y_i|^2 - 2 x_i.y_i + 1e-8) (Losses.py:15-28): d(a, p), and with a
+    negative also d(a, n) and d(p, n)."""
+    a_sq = torch.sum(anchor * anchor, dim=1)
+    p_sq = torch.sum(positive * positive, dim=1)
+    eps = 1e-8
+    d_a_p = torch.sqrt(a_sq + p_sq - 2 * torch.sum(anchor * positive, dim=1) + eps)
+    if negative is not None:
+        n_sq = torch.sum(negative * negative, dim=1)
+        d_a_n = torch.sqrt(a_sq + n_sq - 2 * torch.sum(anchor * negative, dim=1) + eps)
+        d_p_n = torch.sqrt(p_sq + n_sq - 2 * torch.sum(positive * negative, dim=1) + eps)
+        return d_a_p, d_a_n, d_p_n
+    return d_a_p
+
+
+def loss_random_sampling(anchor, positive, negative, anchor_swap=False, margin=1.0, loss_type="triplet_margin"):
+    """The triplet loss over given negatives (Losses.py:29-55; batch_reduce 'random_global', HardNet.py:402-406):
+    no mining in the batch."""
+    if anchor.size() != positive.size() or anchor.size() != negative.size() or anchor.dim() != 2:
+        raise ValueError("anchor, positive and negative must be 2-D tensors of the same shape")
+    eps = 1e-8
+    pos, d_a_n, d_p_n = distance_vectors_pairwise(anchor, positive, negative)
+    min_neg = torch.min(d_a_n, d_p_n) if anchor_swap else d_a_n
+    if loss_type == "triplet_margin":
+        loss = torch.clamp(margin + pos - min_neg, min=0.0)
+    elif loss_type == "softmax":
+        exp_pos = torch.exp(2.0 - pos)
+        loss = -torch.log(exp_pos / (exp_pos + torch.exp(2.0 - min_neg) + eps))
+    elif loss_type == "contrastive":
+        loss = torch.clamp(margin - min_neg, min=0.0) + pos
+    else:
+        raise ValueError(f"unknown loss_type {loss_type!r} (triplet_margin, softmax or contrastive)")
+    return torch.mean(loss)
+
+
+def global_orthogonal_regularization(anchor, negative):
+    """mean(a_i.n_i)^2 + max(mean((a_i.n_i)^2) - 1/dim, 0) (Losses.py:156-162; --gor, HardNet.py:418-419)."""
+    neg_dis = torch.sum(torch.mul(anchor, negative), 1)
+    dim = anchor.size(1)
+    return torch.pow(torch.mean(neg_dis), 2) + torch.clamp(torch.mean(torch.pow(neg_dis, 2)) - 1.0 / dim, min=0.0)
+
+
+class CorrelationPenaltyLoss(torch.nn.Module):
+    """The Frobenius norm of the off-diagonal of the descriptors' scatter matrix over the batch size
+    (HardNet.py:42-53; --decor, HardNet.py:415-416)."""
+
+    def forward(self, input):
+        zeroed = input - torch.mean(input, dim=0).expand_as(input)
+        cor_mat = torch.t(zeroed) @ zeroed
+        no_diag = cor_mat - torch.diag(torch.diag(cor_mat))
+        return torch.sqrt((no_diag * no_diag).sum()) / input.size(0)
 
 
 class SupernetLoss(torch.nn.Module):

@@ -183,6 +183,9 @@ int hn_hardnet_loss_backward(const float* d_anchor, const float* d_positive, int
                              float* d_grad_anchor, float* d_grad_positive, void* d_saved, size_t saved_bytes,
                              void* hip_stream);
 
+/* Train-mode loss_HardNet's other two reductions, 'average' and 'random' (hn_hardnet_loss_reduce_*): declared in
+ * hardnet_mi355x_loss_reduce.h, which this header includes at its end. */
+
 /* FDLNet's neighbour-mask descriptor loss (FDLNet-master/latency/NASNet/model/des.py:57-96, the hard loss of
  * model/network.py:307-309) and its backward, without an N x N matrix:
  *   D_ij  = sqrt(min(max(2 - 2 a_i.p_j, 1e-8), 4))  (exact fp32 dot products; rows need not be unit vectors)
@@ -631,5 +634,7 @@ int hn_abi_version(void);
 #ifdef __cplusplus
 }
 #endif
+
+#include "hardnet_mi355x_loss_reduce.h"
 
 #endif /* HARDNET_MI355X_H */
