@@ -135,7 +135,7 @@ _PROTOTYPES = {
     "hn_abi_version": (),
 }
 # every function returns int (ctypes' default restype) but these
-_RESTYPES = {"hn_det_destroy": None, "hn_destroy": None, "hn_last_error": ctypes.c_char_p}
+_RESTYPES = {"hn_det_destroy": None, "hn_rfdet_destroy": None, "hn_destroy": None, "hn_last_error": ctypes.c_char_p}
 EXPORTED = list(_PROTOTYPES)
 # the extension header include/hardnet_mi355x_loss_reduce.h: loss_HardNet's 'average' and 'random' reductions
 # (tests/test_loss_reduce_abi.py compares this table with that header)
@@ -145,6 +145,17 @@ _LOSS_REDUCE_PROTOTYPES = {
     "hn_hardnet_loss_reduce_backward": (P, P, P, I64, I32, I32, I32, F32, I32, P, P, P, P, S, P),
 }
 EXPORTED_LOSS_REDUCE = list(_LOSS_REDUCE_PROTOTYPES)
+# the extension header include/hardnet_mi355x_rfdet.h: RF-Net's ten-scale detector (tests/test_rfdet.py compares
+# this table with that header)
+_RFDET_PROTOTYPES = {
+    "hn_rfdet_param_count": (SP,),
+    "hn_rfdet_create": (P, S, P, F32, F32, F32, PP),
+    "hn_rfdet_workspace_bytes": (I64, I32, I32, SP),
+    "hn_rfdet_forward": (P, P, I64, I32, I32, P, P, P, P, S, P),
+    "hn_rfdet_destroy": (P,),
+}
+EXPORTED_RFDET = list(_RFDET_PROTOTYPES)
+RFDET_PARAM_FLOATS = 21890  # hn_rfdet_param_count
 
 
 def lib_path() -> str:
@@ -164,7 +175,8 @@ def load_library():
                 f"hardnetnas_amd native library not found at {path}; build it with "
                 "`python -c 'import __graft_entry__ as g; g.build()'` (make -C hardnetnas_amd/csrc)")
         lib = ctypes.CDLL(path)
-        for name, argtypes in list(_PROTOTYPES.items()) + list(_LOSS_REDUCE_PROTOTYPES.items()):
+        for name, argtypes in (list(_PROTOTYPES.items()) + list(_LOSS_REDUCE_PROTOTYPES.items())
+                               + list(_RFDET_PROTOTYPES.items())):
             fn = getattr(lib, name)
             fn.argtypes = list(argtypes)
             if name in _RESTYPES:
@@ -302,8 +314,8 @@ def state_dict_blob(sd: Dict[str, torch.Tensor]) -> np.ndarray:
 
 
 def desc_for_module(module) -> HnArchDesc:
-    from .model import HardNet, HardNetNAS, HardNetNeiMask
-    if isinstance(module, HardNet):
+    from .model import HardNet, HardNetNAS, HardNetNeiMask, RFDes
+    if isinstance(module, (HardNet, RFDes)):  # RFDes: HardNet's body (the Dropout holds no state), 1e-8 / no eps
         return hardnet_desc(module.input_norm_eps, module.l2_eps)
     if isinstance(module, HardNetNeiMask):
         return fdl_desc(module.variant, module.input_norm_eps)
@@ -770,6 +782,66 @@ class NativeDetector:
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             self.lib.hn_det_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class NativeRFDetector:
+    """RF-Net's ten-scale detector on the device (hn_rfdet_create, include/hardnet_mi355x_rfdet.h): ``blob`` is
+    ``state_dict_blob`` of an ``RFDetSO.state_dict()`` (21,890 floats: per level conv_k, insnorm_k, conv_s*,
+    insnorm_s*; then conv_o3 .. conv_o21), ``scale_list`` its ten scales."""
+
+    def __init__(self, blob: np.ndarray, scale_list, device, in_eps: float = 1e-5, score_com_strength: float = 100.0,
+                 scale_com_strength: float = 100.0):
+        self.lib = load_library()
+        self.device = torch.device(device)
+        n = _size("hn_rfdet_param_count")
+        if n != blob.size:
+            raise ValueError(f"parameter blob has {blob.size} floats, library expects {n}")
+        scales = np.ascontiguousarray(np.asarray(scale_list, dtype=np.float32).reshape(-1))
+        if scales.size != 10:
+            raise ValueError(f"scale_list has {scales.size} values, the detector has 10 levels")
+        h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _check(self.lib.hn_rfdet_create(blob.ctypes.data, blob.size, scales.ctypes.data, in_eps,
+                                            score_com_strength, scale_com_strength, h), "hn_rfdet_create")
+        self._h = h
+        self._ws = None  # workspace cache: grows, never shrinks
+
+    def workspace_bytes(self, n_images: int, height: int, width: int) -> int:
+        return _size("hn_rfdet_workspace_bytes", n_images, height, width)
+
+    def forward(self, images: torch.Tensor, score: Optional[torch.Tensor] = None,
+                scale: Optional[torch.Tensor] = None, ori: Optional[torch.Tensor] = None,
+                workspace: Optional[torch.Tensor] = None):
+        """images fp32 [B,1,H,W] -> (score [B,H,W], scale [B,H,W], ori [B,H,W,2]).  The workspace is cached on the
+        object (or pass one of at least workspace_bytes(B, H, W) bytes, as under graph capture of several shapes)."""
+        if images.device != self.device or images.dtype != torch.float32 or images.dim() != 4 or images.shape[1] != 1:
+            raise ValueError(f"expected fp32 [B,1,H,W] on {self.device}, got {images.dtype} {tuple(images.shape)} "
+                             f"on {images.device}")
+        x = images.contiguous()
+        b, _, h, w = x.shape
+        score = _out(score, (b, h, w), self.device, "score")
+        scale = _out(scale, (b, h, w), self.device, "scale")
+        ori = _out(ori, (b, h, w, 2), self.device, "ori")
+        need = self.workspace_bytes(b, h, w)
+        if workspace is None:  # the grow-only cache: replaced when it is too small for this call
+            workspace = self._ws = _workspace(self._ws, need, self.device)
+        else:  # a short one is the C ABI's HN_ERR_WORKSPACE
+            workspace = _workspace(workspace, need, self.device, too_small="pass")
+        _call(self.device, "hn_rfdet_forward", self._h, x, b, h, w, score, scale, ori, *_buf(workspace))
+        return score, scale, ori
+
+    __call__ = forward
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self.lib.hn_rfdet_destroy(self._h)
             self._h = ctypes.c_void_p()
 
     def __del__(self):

@@ -268,6 +268,12 @@ int64_t hn_det_parts(int H, int W);  // partial-statistics slots (k_det_feat wor
 size_t hn_det_ws_bytes(int64_t B, int H, int W);
 hipError_t hn_launch_det(const float* params, float in_eps, const float* images, int64_t B, int H, int W, float* score,
                          float* ori, void* ws, hipStream_t st);
+// RF-Net's ten-scale detector (hn_rfdet.hip; the parameter layout and the workspace plan are hn_rfdet.h's)
+int64_t hn_rfdet_parts(int H, int W);  // layer-kernel workgroups per image
+size_t hn_rfdet_ws_bytes(int64_t B, int H, int W);
+hipError_t hn_launch_rfdet(const float* params, float in_eps, float score_com_strength, float scale_com_strength,
+                           const float* images, int64_t B, int H, int W, float* score, float* scale, float* ori,
+                           void* ws, hipStream_t st);
 // the detector in train() (hn_det_train.hip): T / G are host arrays of 40 device pointers, RFDet.state_dict() order
 void hn_det_train_plan(int64_t n, int H, int W, size_t* saved, size_t* scratch);
 bool hn_det_train_is_param(int slot);  // false for the running statistics' slots

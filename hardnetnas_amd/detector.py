@@ -16,6 +16,10 @@ by operation and in fp64 are the ground truth of the tests.
 (value descending, flat index ascending) -- a stable descending sort -- where the reference leaves ties to
 ``torch.sort``; a NaN score counts as 0.  Where no cut falls inside a group of equal values the two agree.
 
+``RFDetSO`` is RF-Net's detector (rfnet/model/rf_det_so.py), the one with real scale selection: ten levels, a scale
+and an orientation per pixel; in eval mode on HIP fp32 images its ``forward`` runs ``hn_rfdet_forward``
+(hn_rfdet.hip) and everywhere else its torch layers.  It shares ``process``, ``loss`` and the initialisers with ``RFDet``.
+
 ``detect`` is image -> keypoints and ``detect_and_describe`` image -> descriptors (the reference ``inference``
 tuple), with no torch kernel and no host synchronisation between the image and the descriptors on the native path.
 """
@@ -64,15 +68,20 @@ def soft_nms_3d(scale_logits, ksize, com_strength):
     return (e / (s + 1e-8)).permute(0, 2, 3, 1)
 
 
-def soft_max_and_argmax_1d(input, scale_list, com_strength1, com_strength2):
-    """utils/image_utils.py:332-367 (dim -1, keepdim): (score_map, scale_map)."""
+def soft_max_and_argmax_1d(input, scale_list, com_strength1, com_strength2, orint_maps=None):
+    """utils/image_utils.py:332-367 (dim -1, keepdim): (score_map, scale_map); with ``orint_maps`` [..., C, 2] the
+    three-output form of rfnet/utils/image_utils.py:332-375: (score_map, scale_map, orint_map [..., 1, 2])."""
     mx = input.max(dim=-1, keepdim=True)[0]
     e1 = torch.exp(com_strength1 * (input - mx))
     e2 = torch.exp(com_strength2 * (input - mx))
     s1 = e1 / (e1.sum(dim=-1, keepdim=True) + 1e-8)
     s2 = e2 / (e2.sum(dim=-1, keepdim=True) + 1e-8)
     scale_list = scale_list.view(*([1] * (input.dim() - 1)), -1).to(device=input.device, dtype=input.dtype)
-    return (input * s1).sum(dim=-1, keepdim=True), (scale_list * s2).sum(dim=-1, keepdim=True)
+    score_map, scale_map = (input * s1).sum(dim=-1, keepdim=True), (scale_list * s2).sum(dim=-1, keepdim=True)
+    if orint_maps is None:
+        return score_map, scale_map
+    orint_map = (orint_maps * s1.unsqueeze(-1)).sum(dim=-2, keepdim=True)
+    return score_map, scale_map, orint_map / torch.norm(orint_map, p=2, dim=-1, keepdim=True)
 
 
 def gauss_filter_weight(ksize, sig):
@@ -163,7 +172,54 @@ def select_keypoints_torch(score, border, nms_thresh, nms_ksize, topk, gauss_ksi
     return kpts, kscore, kscale, kori, q, mask.to(torch.uint8), v
 
 
-class RFDet(nn.Module):
+class _DetectorBase(nn.Module):
+    """What RFDet and RFDetSO share (model/det.py:96-166 is rfnet/model/rf_det_module.py:182-244): ``process``,
+    ``loss``, the initialisers and the selection arguments, over the attributes both constructors set."""
+
+    def _select_args(self):
+        return (BORDER, float(self.NMS_THRESH), int(self.NMS_KSIZE), int(self.TOPK), int(self.GAUSSIAN_KSIZE),
+                float(self.GAUSSIAN_SIGMA))
+
+    def process(self, im1w_score):
+        """nms, top-K and Gaussian blur of a [B,H,W,1] score map (model/det.py:96-133):
+        (processed score, top-K mask uint8, NMS'd score), each [B,H,W,1]."""
+        s = im1w_score.squeeze(-1)
+        if (s.is_cuda and s.dtype == torch.float32 and s.shape[0] > 0
+                and not (torch.is_grad_enabled() and s.requires_grad)):
+            from . import _native
+            out = _native.select_keypoints(s.detach(), *self._select_args(), dense=True)
+            # the NMS'd score is no output of the C ABI (inference never reads it): a pad and a max-pool in torch
+            v = _nms_value(s.detach(), BORDER, float(self.NMS_THRESH), int(self.NMS_KSIZE))
+            return out["score_proc"].unsqueeze(-1), out["topk_mask"].unsqueeze(-1), v.unsqueeze(-1)
+        _, _, _, _, q, mask, v = select_keypoints_torch(s, *self._select_args())
+        return q.unsqueeze(-1), mask.unsqueeze(-1), v.unsqueeze(-1)
+
+    @staticmethod
+    def loss(left_score, im1gt_score, im1visible_mask):
+        l2_element_diff = (left_score - im1gt_score) ** 2
+        Nvi = torch.clamp(im1visible_mask.sum(dim=(3, 2, 1)), min=2.0)
+        return (torch.sum(l2_element_diff * im1visible_mask, dim=(3, 2, 1)) / (Nvi + 1e-8)).mean()
+
+    @staticmethod
+    def weights_init(m):
+        if isinstance(m, nn.Conv2d):
+            nn.init.xavier_uniform_(m.weight.data, gain=nn.init.calculate_gain("leaky_relu"))
+            try:
+                nn.init.xavier_uniform_(m.bias.data)
+            except Exception:
+                pass
+
+    @staticmethod
+    def convO_init(m):
+        if isinstance(m, nn.Conv2d):
+            nn.init.zeros_(m.weight.data)
+            try:
+                nn.init.ones_(m.bias.data)
+            except Exception:
+                pass
+
+
+class RFDet(_DetectorBase):
     """model/det.py:14-166 (NASNet variant: one scale, 32)."""
 
     def __init__(self, score_com_strength, scale_com_strength, nms_thresh, nms_ksize, topk, gauss_ksize, gauss_sigma):
@@ -264,63 +320,147 @@ class RFDet(nn.Module):
                                                       self.scale_com_strength)
         return score_map, scale_map, ori_map
 
-    def _select_args(self):
-        return (BORDER, float(self.NMS_THRESH), int(self.NMS_KSIZE), int(self.TOPK), int(self.GAUSSIAN_KSIZE),
-                float(self.GAUSSIAN_SIGMA))
 
-    def process(self, im1w_score):
-        """nms, top-K and Gaussian blur of a [B,H,W,1] score map (model/det.py:96-133):
-        (processed score, top-K mask uint8, NMS'd score), each [B,H,W,1]."""
-        s = im1w_score.squeeze(-1)
-        if (s.is_cuda and s.dtype == torch.float32 and s.shape[0] > 0
-                and not (torch.is_grad_enabled() and s.requires_grad)):
-            from . import _native
-            out = _native.select_keypoints(s.detach(), *self._select_args(), dense=True)
-            # the NMS'd score is no output of the C ABI (inference never reads it): a pad and a max-pool in torch
-            v = _nms_value(s.detach(), BORDER, float(self.NMS_THRESH), int(self.NMS_KSIZE))
-            return out["score_proc"].unsqueeze(-1), out["topk_mask"].unsqueeze(-1), v.unsqueeze(-1)
-        _, _, _, _, q, mask, v = select_keypoints_torch(s, *self._select_args())
-        return q.unsqueeze(-1), mask.unsqueeze(-1), v.unsqueeze(-1)
+RF_LEVELS = (3, 5, 7, 9, 11, 13, 15, 17, 19, 21)  # the receptive fields that name RFDetSO's heads
+RF_SOFT_NMS_STRENGTH = 3.0                        # soft_nms_3d's com_strength in RFDetSO.forward (rf_det_so.py:220)
+
+
+class RFDetSO(_DetectorBase):
+    """RF-Net's detector (rfnet/model/rf_det_so.py over rf_det_module.py): ten receptive-field levels 3 .. 21, a
+    score head and an orientation head at each, scale selection by a 3-D soft NMS over (y, x, level).  The
+    reference's constructor arguments, attributes and ``state_dict`` keys.  ``forward`` returns ``score [B,H,W,1]``,
+    ``scale [B,H,W,1]``, ``ori [B,H,W,1,2]`` on every path: in eval mode on HIP fp32 ``[B,1,H,W]`` images with no
+    autograd graph to record and ksize / padding / dilation 3 / 1 / 1 it runs ``hn_rfdet_forward`` (hn_rfdet.hip);
+    everywhere else -- CPU, fp64, ``train()``, autograd -- the torch layers."""
+
+    def __init__(self, score_com_strength, scale_com_strength, nms_thresh, nms_ksize, topk, gauss_ksize, gauss_sigma,
+                 ksize, padding, dilation, scale_list):
+        super().__init__()
+        self.score_com_strength = score_com_strength
+        self.scale_com_strength = scale_com_strength
+        self.NMS_THRESH = nms_thresh
+        self.NMS_KSIZE = nms_ksize
+        self.TOPK = topk
+        self.GAUSSIAN_KSIZE = gauss_ksize
+        self.GAUSSIAN_SIGMA = gauss_sigma
+        self._conv_geometry = (ksize, padding, dilation)
+        for k, rf in enumerate(RF_LEVELS, start=1):  # registration order = the reference's state_dict order
+            setattr(self, f"conv{k}", nn.Conv2d(1 if k == 1 else 16, 16, kernel_size=ksize, stride=1, padding=padding,
+                                                dilation=dilation))
+            setattr(self, f"insnorm{k}", nn.InstanceNorm2d(16, affine=True))
+            setattr(self, f"conv_s{rf}", nn.Conv2d(16, 1, kernel_size=1, stride=1, padding=0))
+            setattr(self, f"insnorm_s{rf}", nn.InstanceNorm2d(1, affine=True))
+        self.scale_list = torch.tensor(scale_list)
+        for rf in RF_LEVELS:
+            setattr(self, f"conv_o{rf}", nn.Conv2d(16, 2, kernel_size=1, stride=1, padding=0))
+        self._native = None  # (key, NativeRFDetector)
+
+    # ---- native path -------------------------------------------------------------------------------------------
+    def _native_ok(self, photos) -> bool:
+        return (not self.training and photos.is_cuda and photos.dtype == torch.float32 and photos.dim() == 4
+                and photos.shape[1] == 1 and photos.shape[0] > 0 and photos.shape[2] * photos.shape[3] >= 2
+                and self._conv_geometry == (3, 1, 1) and self.scale_list.numel() == len(RF_LEVELS)
+                and self.conv1.weight.device == photos.device
+                and all(p.dtype == torch.float32 for p in self.parameters())
+                and len({getattr(self, n).eps for n in self._insnorm_names()}) == 1
+                and not (torch.is_grad_enabled() and (photos.requires_grad
+                                                      or any(p.requires_grad for p in self.parameters()))))
 
     @staticmethod
-    def loss(left_score, im1gt_score, im1visible_mask):
-        l2_element_diff = (left_score - im1gt_score) ** 2
-        Nvi = torch.clamp(im1visible_mask.sum(dim=(3, 2, 1)), min=2.0)
-        return (torch.sum(l2_element_diff * im1visible_mask, dim=(3, 2, 1)) / (Nvi + 1e-8)).mean()
+    def _insnorm_names():
+        return [f"insnorm{k}" for k in range(1, 11)] + [f"insnorm_s{rf}" for rf in RF_LEVELS]
 
-    @staticmethod
-    def weights_init(m):
-        if isinstance(m, nn.Conv2d):
-            nn.init.xavier_uniform_(m.weight.data, gain=nn.init.calculate_gain("leaky_relu"))
-            try:
-                nn.init.xavier_uniform_(m.bias.data)
-            except Exception:
-                pass
+    def native_detector(self, device):
+        """The NativeRFDetector of the current weights on ``device`` (rebuilt when a tensor of the state changes)."""
+        from . import _native
+        key = ((str(device), float(self.score_com_strength), float(self.scale_com_strength),
+                tuple(self.scale_list.tolist()))
+               + tuple((v.data_ptr(), v._version) for v in (*self.parameters(), *self.buffers())))
+        if self._native is None or self._native[0] != key:
+            self._native = (key, _native.NativeRFDetector(
+                _native.state_dict_blob(self.state_dict()), self.scale_list.float().cpu().numpy(), device,
+                in_eps=self.insnorm1.eps, score_com_strength=float(self.score_com_strength),
+                scale_com_strength=float(self.scale_com_strength)))
+        return self._native[1]
 
-    @staticmethod
-    def convO_init(m):
-        if isinstance(m, nn.Conv2d):
-            nn.init.zeros_(m.weight.data)
-            try:
-                nn.init.ones_(m.bias.data)
-            except Exception:
-                pass
+    def forward_maps(self, photos):
+        """(score [B,H,W], scale [B,H,W], ori [B,H,W,2]) of the native forward."""
+        return self.native_detector(photos.device).forward(photos.detach())
+
+    def _apply(self, fn, *a, **k):
+        self._native = None
+        return super()._apply(fn, *a, **k)
+
+    # ---- the reference's methods -------------------------------------------------------------------------------
+    def forward(self, photos):
+        if self._native_ok(photos):
+            score, scale, ori = self.forward_maps(photos)
+            return score.unsqueeze(-1), scale.unsqueeze(-1), ori.unsqueeze(-2)
+        return self.forward_torch(photos)
+
+    def forward_torch(self, photos):
+        """The torch layers (rf_det_so.py:74-234), whatever the device: the CPU / fp64 / training path."""
+        feat, scores, orints = photos, [], []
+        for k, rf in enumerate(RF_LEVELS, start=1):
+            h = F.leaky_relu(getattr(self, f"insnorm{k}")(getattr(self, f"conv{k}")(feat)))
+            scores.append(getattr(self, f"insnorm_s{rf}")(getattr(self, f"conv_s{rf}")(h)).permute(0, 2, 3, 1))
+            o = getattr(self, f"conv_o{rf}")(h)
+            orints.append((o / torch.norm(o, p=2, dim=1, keepdim=True)).permute(0, 2, 3, 1).unsqueeze(-2))
+            feat = h if k == 1 else h + feat  # the heads read h before the residual; feat_10 is never read
+        score_maps = torch.cat(scores, -1)    # [B,H,W,10]
+        orint_maps = torch.cat(orints, -2)    # [B,H,W,10,2]
+        scale_probs = soft_nms_3d(score_maps, ksize=SOFT_NMS_KSIZE, com_strength=RF_SOFT_NMS_STRENGTH)
+        return soft_max_and_argmax_1d(scale_probs, self.scale_list, self.score_com_strength, self.scale_com_strength,
+                                      orint_maps=orint_maps)
+
+
+def randomise_rfdet_(det, seed):
+    """Seeded, non-degenerate weights for the tests and the benchmark -- the distributions of the fixture
+    tests/golden/rfdet.npz -- on a module with RFDetSO's attribute names (the reference's or this
+    package's): ``weights_init`` under ``torch.manual_seed(seed)``; then from a generator seeded ``seed + 1`` the
+    InstanceNorm affine parameters weight 0.75 + 0.5 U, bias 0.2 N, and the conv_o* heads weight 0.3 N, bias
+    +-(0.5 + U) (convO_init's zeros and ones would make every orientation the same constant).  The two signs are
+    drawn once for the detector, not per level: the final orientation is close to the mean of the ten unit vectors
+    (the softmax over levels is nearly flat), and with independent signs per level that mean cancels to a norm
+    below the exclusion floor on ~3 % of the pixels.  Returns det.eval()."""
+    torch.manual_seed(seed)
+    det.apply(det.weights_init)
+    g = torch.Generator().manual_seed(seed + 1)
+    with torch.no_grad():
+        for m in det.modules():
+            if isinstance(m, nn.InstanceNorm2d):
+                m.weight.copy_(0.75 + 0.5 * torch.rand(m.num_features, generator=g))
+                m.bias.copy_(0.2 * torch.randn(m.num_features, generator=g))
+        sign = torch.where(torch.rand(2, generator=g) < 0.5, -1.0, 1.0)
+        for rf in RF_LEVELS:
+            conv = getattr(det, f"conv_o{rf}")
+            conv.weight.copy_(0.3 * torch.randn(conv.weight.shape, generator=g))
+            conv.bias.copy_(sign * (0.5 + torch.rand(2, generator=g)))
+    return det.eval()
 
 
 def detect(det, im_data):
-    """Image -> keypoints (model/network.py:155-162, 181-182): ``(kpts [B K,4] int64 rows (b, y, x, 0) in raster
-    order per image, kscale [B K], kori [B K,2], kscore [B K], im_scale [B,H,W,1])``, K = ``det.TOPK``.  On the
-    native path this is ``hn_det_forward`` followed by ``hn_select_keypoints``, bit for bit."""
+    """Image -> keypoints (model/network.py:155-162, 181-182; rfnet/model/rf_net_so.py:160-168): ``(kpts [B K,4]
+    int64 rows (b, y, x, 0) in raster order per image, kscale [B K], kori [B K,2], kscore [B K], im_scale
+    [B,H,W,1])``, K = ``det.TOPK``.  On the native path this is ``hn_det_forward`` (``RFDet``: one constant scale)
+    or ``hn_rfdet_forward`` (``RFDetSO``: its scale map, so ``kscale`` varies per keypoint) followed by
+    ``hn_select_keypoints``, bit for bit.  An orientation map ``[B,H,W,1,2]`` is taken as ``[B,H,W,2]``."""
     if det._native_ok(im_data):
         from . import _native
-        score, ori = det.forward_maps(im_data)
+        maps = det.forward_maps(im_data)
+        if len(maps) == 3:  # a detector with a scale map
+            score, scale, ori = maps
+            out = _native.select_keypoints(score, *det._select_args(), scale_map=scale, ori_map=ori)
+            return out["kpts"], out["kscale"], out["kori"], out["kscore"], scale.unsqueeze(-1)
+        score, ori = maps
         scale_value = float(det.scale_list[0])
         out = _native.select_keypoints(score, *det._select_args(), scale_value=scale_value, ori_map=ori)
         im_scale = torch.full((), scale_value, device=score.device).expand(*score.shape, 1)
         return out["kpts"], out["kscale"], out["kori"], out["kscore"], im_scale
     im_rawsc, im_scale, im_orint = det(im_data)
     kpts, kscore, kscale, kori, _, _, _ = select_keypoints_torch(
-        im_rawsc.squeeze(-1), *det._select_args(), scale_map=im_scale.squeeze(-1), ori_map=im_orint)
+        im_rawsc.squeeze(-1), *det._select_args(), scale_map=im_scale.squeeze(-1),
+        ori_map=im_orint.reshape(*im_rawsc.shape[:3], 2))
     return kpts, kscale, kori, kscore, im_scale
 
 

@@ -212,6 +212,52 @@ class HardNet(_NativeMixin, nn.Module):
         return x / norm.unsqueeze(-1)
 
 
+class RFDes(_NativeMixin, nn.Module):
+    """RF-Net's descriptor (FDLNet-master/latency/rfnet/model/rf_des.py, ``HardNetNeiMask`` there): HardNet's body
+    without the Dropout, so its conv layers are ``features.{0,3,6,9,12,15,18}``; ``input_norm`` eps 1e-8, L2 by
+    ``torch.norm`` with no eps, ``loss`` the neighbour-mask loss.  In eval mode it runs the stock HardNet kernels
+    through ``hardnet_desc(1e-8, 0.0)`` (the parameter blob is HardNet's: the Dropout holds no state); in ``train()``
+    its torch layers."""
+
+    def __init__(self, MARGIN: float = 1.0, C: float = 1.0, strict: bool = False):
+        super().__init__()
+        self.native_strict = strict
+        self.MARGIN, self.C = MARGIN, C
+        layers = []
+        for i, (ci, co, k, s) in enumerate(((1, 32, 3, 1), (32, 32, 3, 1), (32, 64, 3, 2), (64, 64, 3, 1),
+                                            (64, 128, 3, 2), (128, 128, 3, 1), (128, 128, 8, 1))):
+            layers += [nn.Conv2d(ci, co, kernel_size=k, stride=s, padding=1 if k == 3 else 0, bias=False),
+                       nn.BatchNorm2d(co, affine=False)]
+            if i < 6:
+                layers.append(nn.ReLU())
+        self.features = nn.Sequential(*layers)
+        self.input_norm_eps = 1e-8
+        self.l2_eps = 0.0
+
+    def input_norm(self, x):
+        flat = x.view(x.size(0), -1)
+        mp = torch.mean(flat, dim=1)
+        sp = torch.std(flat, dim=1) + self.input_norm_eps
+        return (x - mp.detach().view(-1, 1, 1, 1)) / sp.detach().view(-1, 1, 1, 1)
+
+    def forward(self, input):
+        y = self._dispatch_native(input)
+        if y is not None:
+            return y
+        x_features = self.features(self.input_norm(input))
+        x = x_features.view(x_features.size(0), -1)
+        return x / torch.norm(x, p=2, dim=-1, keepdim=True)
+
+    def loss(self, anchor, positive, anchor_kp, positive_kp):
+        from .losses import loss_neimask
+        return loss_neimask(anchor, positive, anchor_kp, positive_kp, margin=self.MARGIN, C=self.C)
+
+    @staticmethod
+    def weights_init(m):
+        """rf_des.py:98-105: HardNet's initialiser (orthogonal, gain 0.6)."""
+        weights_init(m)
+
+
 def weights_init(m):
     """HardNet.py:317-324 (orthogonal, gain 0.6)."""
     if isinstance(m, nn.Conv2d):

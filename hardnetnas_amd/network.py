@@ -335,6 +335,10 @@ class Network(nn.Module):
         if not (self.PSIZE == NATIVE_PSIZE and hasattr(det, "_native_ok") and hasattr(det, "forward_maps")
                 and isinstance(self.des, _NativeMixin) and int(det.TOPK) >= 1):
             return False
+        if det.scale_list.numel() != 1:
+            # _forward_native passes the one constant scale to the ground-truth stage; a detector with a scale map
+            # (RFDetSO) takes the reference-order path below, which carries the maps
+            return False
         if not (det._native_ok(im1_data) and det._native_ok(im2_data) and im1_data.shape == im2_data.shape
                 and im1_data.shape[2] > 2 * BORDER and im1_data.shape[3] > 2 * BORDER
                 and int(det.TOPK) <= im1_data.shape[2] * im1_data.shape[3]):

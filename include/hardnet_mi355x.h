@@ -636,5 +636,6 @@ int hn_abi_version(void);
 #endif
 
 #include "hardnet_mi355x_loss_reduce.h"
+#include "hardnet_mi355x_rfdet.h"
 
 #endif /* HARDNET_MI355X_H */
